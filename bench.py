@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: k=2 De Bruijn lift of a synthetic temporal edge stream + one DBGNN train step, on 1..N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with the per-kernel figures of the timed steps themselves).
+``--full`` adds everything measured outside the timed steps: the generic-kernel lift / aggregation / line-graph rooflines, the step through the
+reference API, the hub streams, the multi-order builds and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step computed
+(loss, weights after the update, their gradients, seeded samples of both layers' GCN plans) as DIR/<name>.npy.
 
 ``--gpus N`` with N > 1 and no RANK in the environment re-launches itself under ``torch.distributed.run`` (one process per GPU,
 backend nccl = RCCL over xGMI, rendezvous on 127.0.0.1); when the driver already started it that way the ranks are taken from the
@@ -18,8 +23,9 @@ environment.  One STEP = one pass of the hot path over the synthetic events, whi
 Workload (SURVEY.md §8d "10M temporal edges" headline of BASELINE.json): temporal ER stream, m = 10^7 events, N = 5*10^5 nodes,
 int64 timestamps uniform in [0, 10^7), delta = 10^6 (E2 ~ 1.9*10^7), 64-dim features, hidden_dims [64, 64, 64], 8 classes, fp32.
 The JSON line follows the driver's contract and adds `roofline` (the most expensive (kernel, graph) pair, live HIP-event timing),
-`kernel_rooflines` (every timed kernel per graph), `lift_roofline` / `aggregation_roofline` (SURVEY §8d bytes over the whole
-lift / aggregation incl. their sorts and scans) and `cpu_baseline` (BASELINE.md §3 protocol, bounded).
+`kernel_rooflines` (every timed kernel per graph), and with --full `lift_roofline` / `aggregation_roofline` (SURVEY §8d bytes over the
+whole lift / aggregation incl. their sorts and scans), `api_path`, `hub_streams`, `multi_order` and `cpu_baseline` (BASELINE.md §3
+protocol, bounded).
 """
 from __future__ import annotations
 
@@ -84,7 +90,14 @@ def parse():
     ap.add_argument("--cpu-baseline-only", action="store_true", help="run only the CPU baseline and print its JSON (used by the main run, in a "
                                                                       "subprocess with a hard time limit, so that it can never stall the bench line)")
     ap.add_argument("--cpu-baseline-timeout", type=int, default=1200)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also measure what lies outside the timed steps (generic-kernel rooflines, API path, hub "
+                                                        "streams, multi-order builds, line-graph lift, CPU baseline); a plain run does none of it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                                                                      "large arrays as a fixed seeded sample, < 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class ResidentRows:
@@ -786,6 +799,47 @@ def emulate(args) -> int:
     return 0
 
 
+DUMP_SAMPLE = 1 << 18          # entries kept of a larger array (float64: 2 MB each)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir: str, loss, net, shard) -> None:
+    """`--dump-outputs`: what the last timed step handed its caller — the loss, the weights after the optimiser step and their gradients —
+    and the graph it built (first- and order-2 GCN plans of `shard`, partition path).  Integer arrays as float64 (exact below 2^53); an
+    array of more than DUMP_SAMPLE entries is replaced by the entries at DUMP_SAMPLE indices drawn with a fixed seed (`<name>.sample_idx`)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().to(torch.float64).reshape(1)}
+    for name, p in net.named_parameters():
+        arrays[f"param.{name}"] = p.detach().float()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach().float()
+    if shard is not None:
+        for layer, plan in (("fo", shard.fo.plan), ("ho", shard.ho.plan)):
+            n_dst = int(plan.n_dst)
+            ptr = plan.fwd_ptr[: n_dst + 1]
+            nnz = int(ptr[-1])
+            arrays[f"plan_{layer}.fwd_ptr"] = ptr
+            arrays[f"plan_{layer}.fwd_idx"] = plan.fwd_idx[:nnz]
+            if plan.fwd_val is not None:
+                arrays[f"plan_{layer}.fwd_val"] = plan.fwd_val[:nnz]
+            if plan.self_coef is not None:
+                arrays[f"plan_{layer}.self_coef"] = plan.self_coef[:n_dst]
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(12345).integers(0, t.numel(), DUMP_SAMPLE))
+            np.save(os.path.join(out_dir, f"{name}.sample_idx.npy"), idx.astype(np.float64))
+            total += idx.size * 8
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float32 if a.dtype in (np.float32, np.float16) else np.float64)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        total += a.nbytes
+    assert total <= DUMP_LIMIT, f"--dump-outputs wrote {total} bytes (limit {DUMP_LIMIT})"
+
+
 def main() -> int:
     args = parse()
     if args.cpu_baseline_only:
@@ -974,7 +1028,9 @@ def main() -> int:
         for c in clocks:
             c.enabled = False
         fused_ran = bool(fused_clock.records)
-        if fused_ran and rank == 0 and world == 1:
+        if args.dump_outputs and rank == 0:            # (before anything else runs on the GPU: the buffers of the last timed step are intact)
+            dump_outputs(args.dump_outputs, loss, net, getattr(step_partition, "last_shard", None) if partition else None)
+        if fused_ran and rank == 0 and world == 1 and args.full:
             # the fused builder never writes the event graph: the lift / aggregation kernels it replaces (and the k_expand fill kernel the
             # north star's "40 % of HBM peak on the lift kernel" refers to) are timed here, OUTSIDE the timed region, on the same stream
             ppd.FUSED_BUILDER = False
@@ -998,7 +1054,7 @@ def main() -> int:
         sizes.update(ppd.global_sizes(step_partition.last_shard, comm))       # (A2 over all ranks: a collective, outside the timed region)
         step_partition.last_shard = None                                       # (the API steps below must not add this shard to the peak)
     peak_main = torch.cuda.max_memory_allocated(dev)
-    if partition and rank == 0 and world == 1 and not args.no_api_path:
+    if partition and rank == 0 and world == 1 and args.full and not args.no_api_path:
         torch.cuda.reset_peak_memory_stats(dev)
         api_sizes = dict(sizes)
         for _ in range(max(3, min(args.warmup, 5))):
@@ -1023,14 +1079,14 @@ def main() -> int:
     # Streams with HUB NODES through the same builder (round 5; outside the timed region, rank 0 at one GPU): BASELINE configs[2]'s scale-free
     # generator and a contact stream of the shape of the reference's documented datasets — fused builder against the generic kernels, plans compared
     hub_report = None
-    if partition and rank == 0 and world == 1 and not args.no_hub_streams:
+    if partition and rank == 0 and world == 1 and args.full and not args.no_hub_streams:
         hub_report = hub_streams(dev)
     multi_order_report = None
-    if partition and rank == 0 and world == 1 and not args.no_multi_order:
+    if partition and rank == 0 and world == 1 and args.full and not args.no_multi_order:
         multi_order_report = multi_order(g, args.nodes, args.delta, dev)
     # untimed extra: the k=2 -> k=3 line-graph lift of the same event graph (the lift kernel WITHOUT the continuation-list gather)
     k3 = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ho = pp.algorithms.lift_order_temporal(g, args.delta)
         with KernelClock(L, "pp_linegraph_fill", lambda e, n, total, *r: ("k_expand<no list> (pp_linegraph_fill)", 16 * total + 12 * e)) as lg_clock:
             lg_clock.enabled = True
@@ -1142,6 +1198,9 @@ def main() -> int:
                                      "frac": (agg_bytes / (agg_total_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if agg_total_ms > 0 else 0.0},
             "linegraph_fill_roofline": k3,
         }
+        if not args.full:           # (these need the untimed generic-kernel passes and the line-graph lift that only --full runs)
+            for key in ("lift_roofline", "lift_fill_roofline", "generic_kernels_timed", "aggregation_roofline", "linegraph_fill_roofline"):
+                del line[key]
         if api_path is not None:
             line["api_path_ms_per_step"] = api_path["ms_per_step"]
             line["api_path"] = api_path
@@ -1172,7 +1231,7 @@ def main() -> int:
                     "what": "SURVEY §8d bytes of what the builder REPLACES (lift 24 m + 16 E2, both aggregations) over the builder's time: an "
                             "equivalent-work speed for comparison with lift_roofline / aggregation_roofline, not bandwidth the builder reaches",
                     "algorithmic_bytes": generic_bytes, "GB_per_s": generic_bytes / (f_avg * 1e-3) / 1e9 if f_avg > 0 else 0.0}}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline_isolated(args)
         print(json.dumps(line), flush=True)
     if launched:

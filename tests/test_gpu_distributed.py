@@ -324,10 +324,10 @@ def _bench(extra, timeout=900):
     return json.loads(lines[0])
 
 
-def test_bench_partition_default_and_rccl_world1_and_gloo_world2():
+def test_bench_partition_default_and_rccl_world1_and_gloo_world2(tmp_path):
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
-    one = _bench([])
+    one = _bench(["--full"])
     assert one["n_gpus"] == 1 and one["scaling"] == "strong" and one["roofline"]["frac"] > 0 and one["lift_roofline"]["frac"] > 0
     assert one["aggregation_roofline"]["frac"] > 0 and one["config"]["E2"] > 0
     port = _free_port()
@@ -355,9 +355,19 @@ def test_bench_partition_default_and_rccl_world1_and_gloo_world2():
     assert abs(emulated["loss"] - one["loss"]) < 1e-3 * max(1.0, abs(one["loss"])), (emulated["loss"], one["loss"])
     # BASELINE configs[1] (2M events), forward pass at the initial weights: the 8-way sharded build + partitioned forward against the single-GPU path
     c1 = ["--warmup", "0", "--steps", "1", "--events", "2000000", "--nodes", "100000", "--span", "1000000", "--delta", "100000"]
-    whole, split = _bench(c1), _bench(c1 + ["--emulate-ranks", "8"])
+    dump = tmp_path / "outputs"
+    whole, split = _bench(c1 + ["--dump-outputs", str(dump)]), _bench(c1 + ["--emulate-ranks", "8"])
     assert split["E2"] == whole["config"]["E2"] and split["A2"] == whole["config"]["A2"] and split["U2"] == whole["config"]["U2"]
     assert abs(split["loss"] - whole["loss"]) < 1e-5 * abs(whole["loss"]), (split["loss"], whole["loss"])
+    # a plain run: the headline line without what --full adds; --dump-outputs: the last timed step's loss, weights, gradients and plans
+    assert whole["steps"] == 1 and whole["ms_per_step"] > 0 and whole["value"] > 0
+    assert not {"lift_roofline", "aggregation_roofline", "api_path", "hub_streams", "multi_order", "cpu_baseline"} & set(whole)
+    files = {f.name: np.load(f) for f in dump.glob("*.npy")}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert abs(float(files["loss.npy"][0]) - whole["loss"]) < 1e-6 * abs(whole["loss"])
+    assert any(k.startswith("param.") for k in files) and any(k.startswith("grad.") for k in files)
+    fo_ptr = files["plan_fo.fwd_ptr.npy"]             # (10^5 + 1 entries: below the sampling threshold, written whole)
+    assert fo_ptr.size == 100_001 and fo_ptr[0] == 0 and (np.diff(fo_ptr) >= 0).all() and {"plan_ho.fwd_idx.npy", "plan_ho.fwd_val.npy"} <= set(files)
     # the driver's command shape without a launcher: `python bench.py --gpus N` starts its own ranks
     self_launched = _bench(["--gpus", "2", "--backend", "gloo", "--share-gpu", "--mode", "partition"])
     assert self_launched["n_gpus"] == 2 and self_launched["config"]["E2"] == one["config"]["E2"] and self_launched["scaling"] == "strong"

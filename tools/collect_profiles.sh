@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/profiles
 mkdir -p $OUT
 # (--no-multi-order / --no-hub-streams: those sections run other streams through other kernels after the timed region; the per-dispatch means of the
 # PMC passes are taken over the headline step's launches)
-CMD="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-multi-order --no-hub-streams"
+CMD="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-multi-order --no-hub-streams"
 rm -rf /tmp/p_stats; rocprofv3 --kernel-trace --stats -d /tmp/p_stats -o x -- $CMD > /tmp/log_stats.txt 2>&1
 python $R/tools/rocprof_summary.py $(find /tmp/p_stats -name "*.db" | head -1) --top 70 > $OUT/${TAG}_bench_kernel_stats.txt 2>&1
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -55,6 +55,6 @@ PY
 # the bench line LAST, with the table of THIS profile in place (bench.py reads roofline.traffic from profiles/<TAG>_pmc_traffic.json: the kept line and
 # the table it cites then describe the same tree — VERDICT r5 #10)
 cp $OUT/${TAG}_pmc_traffic.json $R/profiles/${TAG}_pmc_traffic.json
-timeout 900 python $R/bench.py > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_stderr.txt
+timeout 900 python $R/bench.py --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_stderr.txt
 timeout 300 python $R/tools/bench_kernels.py --ops lift,agg,plan,spmm,dense,gcn > $OUT/${TAG}_per_op_timings.txt 2>&1
 tail -c 600 $OUT/${TAG}_bench_line.json

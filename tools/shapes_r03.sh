@@ -2,7 +2,7 @@
 # Run ON the GPU box: bench lines of the non-headline BASELINE shapes + the 8-rank projection, each with >= 3 warm-up steps.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/shapes; mkdir -p $O
 cd $R
-B="timeout 600 python bench.py --no-cpu-baseline --warmup 3"
+B="timeout 600 python bench.py --full --no-cpu-baseline --warmup 3"
 $B --emulate-ranks 8 --steps 5 --trace > $O/emulate8.json 2> $O/emulate8.err
 $B --emulate-ranks 8 --steps 5 --no-overlap > $O/emulate8_no_overlap.json 2>> $O/emulate8.err
 $B --emulate-ranks 4 --steps 5 > $O/emulate4.json 2>> $O/emulate8.err

@@ -2,7 +2,7 @@
 # Run ON the GPU box: bench lines of the non-headline BASELINE shapes (each with >= 3 warm-up steps) and the emulation at 2 / 4 / 8 ranks.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/shapes; mkdir -p $O
 cd $R
-B="timeout 600 python bench.py --no-cpu-baseline --warmup 3"
+B="timeout 600 python bench.py --full --no-cpu-baseline --warmup 3"
 $B --emulate-ranks 4 --steps 5 > $O/emulate4.json 2> $O/emulate.err
 $B --emulate-ranks 2 --steps 5 > $O/emulate2.json 2>> $O/emulate.err
 $B --steps 10 --events 2000000 --nodes 100000 --span 1000000 --delta 100000 > $O/config1.json 2> $O/config1.err
@@ -10,7 +10,7 @@ $B --steps 5 --features 128 > $O/f128.json 2> $O/f128.err
 # configs[4]: one GPU's eighth of the 10^8-event stream at its 256-dim width (the whole stream's DBGNN does not fit one GPU)
 $B --steps 5 --events 12500000 --nodes 625000 --span 12500000 --delta 1250000 --features 256 > $O/config4_per_gpu_share.json 2> $O/config4.err
 # ten times the headline stream on ONE GPU
-timeout 900 python bench.py --no-cpu-baseline --warmup 2 --steps 3 --events 100000000 --nodes 5000000 --span 100000000 --delta 10000000 > $O/events_1e8.json 2> $O/events_1e8.err
+timeout 900 python bench.py --full --no-cpu-baseline --warmup 2 --steps 3 --events 100000000 --nodes 5000000 --span 100000000 --delta 10000000 > $O/events_1e8.json 2> $O/events_1e8.err
 tail -c 200 $O/*.err
 for f in $O/*.json; do echo $f; python -c "
 import json,sys

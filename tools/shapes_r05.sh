@@ -3,7 +3,7 @@
 # emulation at 2 / 4 / 8 ranks, the API flow and the hub streams.  -> gpurun_out/shapes/   (copy to profiles/r05_shapes/)
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/shapes; mkdir -p $O
 cd $R
-B="timeout 600 python bench.py --no-cpu-baseline --warmup 3"
+B="timeout 600 python bench.py --full --no-cpu-baseline --warmup 3"
 $B --emulate-ranks 8 --steps 5 > $O/emulate8.json 2> $O/emulate.err
 $B --emulate-ranks 4 --steps 5 > $O/emulate4.json 2>> $O/emulate.err
 $B --emulate-ranks 2 --steps 5 > $O/emulate2.json 2>> $O/emulate.err
@@ -15,7 +15,7 @@ $B --steps 5 --events 20000000 --nodes 1000000 --features 128 > $O/config3_per_g
 # configs[4]: one GPU's eighth of the 10^8-event stream at its 256-dim width (the whole stream's DBGNN does not fit one GPU)
 $B --steps 5 --events 12500000 --nodes 625000 --span 12500000 --delta 1250000 --features 256 > $O/config4_per_gpu_share.json 2> $O/config4.err
 # ten times the headline stream on ONE GPU
-timeout 900 python bench.py --no-cpu-baseline --warmup 2 --steps 3 --events 100000000 --nodes 5000000 --span 100000000 --delta 10000000 > $O/events_1e8.json 2> $O/events_1e8.err
+timeout 900 python bench.py --full --no-cpu-baseline --warmup 2 --steps 3 --events 100000000 --nodes 5000000 --span 100000000 --delta 10000000 > $O/events_1e8.json 2> $O/events_1e8.err
 timeout 600 python tools/probes/api_flow.py > $O/api_flow.txt 2> $O/api_flow.err
 timeout 600 python tools/probes/hub_streams.py > $O/hub_streams.txt 2> $O/hub_streams.err
 timeout 300 python tools/probes/long_run.py > $O/long_run.txt 2> $O/long_run.err

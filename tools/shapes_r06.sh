@@ -11,7 +11,7 @@ bash tools/probes/prof_script.sh mo5 tools/probes/multi_order_k.py 5 3 > /dev/nu
 { echo "# rocprofv3 --kernel-trace --stats -- python tools/probes/multi_order_k.py 5 3   (3 builds of MultiOrderModel.from_temporal_graph(max_order=5) on the headline stream + the stream's set-up; MI355X)"; cat $R/gpurun_out/stats_mo5.txt; echo; cat $R/gpurun_out/out_mo5.txt; } > $O/multi_order_kernel_stats.txt
 bash tools/probes/prof_script.sh c2k3 tools/probes/config2_k3.py 1500000 3 > /dev/null 2>&1
 { echo "# rocprofv3 --kernel-trace --stats -- python tools/probes/config2_k3.py 1500000 3   (3 builds at max_order=3 on the configs[2] generator; MI355X)"; cat $R/gpurun_out/stats_c2k3.txt; echo; cat $R/gpurun_out/out_c2k3.txt; } > $O/config2_k3_kernel_stats.txt
-B="timeout 600 python bench.py --no-cpu-baseline --warmup 3 --no-multi-order --no-hub-streams"
+B="timeout 600 python bench.py --full --no-cpu-baseline --warmup 3 --no-multi-order --no-hub-streams"
 $B --emulate-ranks 8 --steps 5 > $O/emulate8.json 2> $O/emulate.err
 $B --steps 10 --mode streams > $O/streams_mode.json 2> $O/streams.err
 $B --steps 10 --events 2000000 --nodes 100000 --span 1000000 --delta 100000 > $O/config1.json 2> $O/config1.err
