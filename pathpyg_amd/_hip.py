@@ -187,6 +187,25 @@ def run_together(*gens):
             g.close()
 
 
+def _event_stream(ei: torch.Tensor, time: torch.Tensor, weight: torch.Tensor | None = None):
+    """``(time, weight)`` of the events ``ei`` [2, m] as the temporal kernels take them: timestamps int64 or float64 (narrower integers widened),
+    contiguous, one per event; ``weight`` None or a contiguous float32 vector of m entries.  ``None``: a weight the builders do not take (the
+    caller hands the stream back).  The device is not looked at: every caller runs ``require_device`` first."""
+    if time.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
+        time = time.to(torch.int64)
+    if time.dtype not in (torch.int64, torch.float64):
+        raise TypeError(f"timestamps must be int64 or float64, got {time.dtype}")
+    time = time.contiguous()
+    m = ei.size(1)
+    if time.numel() != m:
+        raise ValueError("time and edge_index disagree on the number of events")
+    if weight is not None:
+        if weight.dtype != torch.float32 or weight.numel() != m:
+            return None
+        weight = weight.contiguous()
+    return time, weight
+
+
 def temporal_lift(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delta, n_own: int | None = None,
                   id_offset: int = 0) -> torch.Tensor:
     """Second-order event graph of a TIME-SORTED event list: all (i, j) with head(i) == tail(j) and
@@ -199,14 +218,8 @@ def temporal_lift_steps(edge_index: torch.Tensor, time: torch.Tensor, num_nodes:
     """:func:`temporal_lift` as a count -> fill generator for :func:`run_together`."""
     ei = _edge_index(edge_index)
     dev = require_device(ei, time)
-    if time.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        time = time.to(torch.int64)
-    if time.dtype not in (torch.int64, torch.float64):
-        raise TypeError(f"timestamps must be int64 or float64, got {time.dtype}")
-    time = time.contiguous()
+    time, _ = _event_stream(ei, time)
     m = ei.size(1)
-    if time.numel() != m:
-        raise ValueError("time and edge_index disagree on the number of events")
     kind, di, df = resolve_delta(time.dtype, delta)
     L = lib()
     # (the device guard is NOT held across the yield: interleaved generators would exit their guards out of order, ADVICE r2)
@@ -778,20 +791,11 @@ def debruijn2(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delt
     2^31 order-2 edges, hub partials beyond 24 GiB; with ``unsorted_ok`` an unsorted stream): the caller then takes the generic path."""
     ei = _edge_index(edge_index)
     dev = require_device(ei, time, weight)
-    if time.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        time = time.to(torch.int64)
-    if time.dtype not in (torch.int64, torch.float64):
-        raise TypeError(f"timestamps must be int64 or float64, got {time.dtype}")
-    time = time.contiguous()
+    stream = _event_stream(ei, time, weight)
     m, n = ei.size(1), int(num_nodes)
-    if time.numel() != m:
-        raise ValueError("time and edge_index disagree on the number of events")
-    if m == 0 or n == 0:
+    if stream is None or m == 0 or n == 0:
         return None
-    if weight is not None:
-        if weight.dtype != torch.float32 or weight.numel() != m:
-            return None
-        weight = weight.contiguous()
+    time, weight = stream
     kind, di, df = resolve_delta(time.dtype, delta)
     L = lib()
     with torch.cuda.device(dev):
@@ -913,20 +917,11 @@ def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
         ev = torch.cuda.Event(enable_timing=True)
         ev.record()
         return ev
-    if time.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        time = time.to(torch.int64)
-    if time.dtype not in (torch.int64, torch.float64):
-        raise TypeError(f"timestamps must be int64 or float64, got {time.dtype}")
-    time = time.contiguous()
+    stream = _event_stream(ei, time, weight)
     m, n = ei.size(1), int(num_nodes)
-    if time.numel() != m:
-        raise ValueError("time and edge_index disagree on the number of events")
-    if m == 0 or n == 0 or m >= _INT32_ROWS:
+    if stream is None or m == 0 or n == 0 or m >= _INT32_ROWS:
         return None
-    if weight is not None:
-        if weight.dtype != torch.float32 or weight.numel() != m:
-            return None
-        weight = weight.contiguous()
+    time, weight = stream
     kind, di, df = resolve_delta(time.dtype, delta)
     L = lib()
     with torch.cuda.device(dev):
@@ -1030,20 +1025,13 @@ def debruijn2_part_count(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
     (a rank-local raise in front of a collective leaves the other ranks blocked in it)."""
     ei = _edge_index(edge_index)
     dev = require_device(ei, time, weight, cuts_dev)
-    if time.dtype in (torch.int32, torch.int16, torch.int8, torch.uint8):
-        time = time.to(torch.int64)
-    if time.dtype not in (torch.int64, torch.float64):
-        raise TypeError(f"timestamps must be int64 or float64, got {time.dtype}")
-    time = time.contiguous()
+    stream = _event_stream(ei, time, weight)
     m, n = ei.size(1), int(num_nodes)
     world = int(cuts_dev.numel()) - 1
     n_own = int(node_hi) - int(node_lo)
-    if m == 0 or n_own <= 0:            # (pp_debruijn2_part_count leaves the shard-level outputs of such a rank unwritten: ADVICE r4)
+    if stream is None or m == 0 or n_own <= 0:      # (pp_debruijn2_part_count leaves the shard-level outputs of such a rank unwritten: ADVICE r4)
         return None
-    if weight is not None:
-        if weight.dtype != torch.float32 or weight.numel() != m:
-            return None
-        weight = weight.contiguous()
+    time, weight = stream
     pad_rows = max(int(pad_rows) if pad_rows is not None else n, 1)          # rows per rank of the padded first-order layout (>= the largest range)
     kind, di, df = resolve_delta(time.dtype, delta)
     L = lib()

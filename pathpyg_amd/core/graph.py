@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .. import _dispatch
-from ..data import Data
+from ..data import Data, moved
 from .index_map import IndexMap
 
 logger = logging.getLogger("pathpyg_amd")
@@ -163,14 +163,9 @@ class Graph:
         return self.data.edge_index.device
 
     def to(self, device) -> "Graph":
-        """Move all tensors to ``device`` in place and return ``self`` (reference graph.py:273-296)."""
-        self.data.edge_index = self.data.edge_index.to(device)
-        self.data.node_sequence = self.data.node_sequence.to(device)
-        for attr in self.node_attrs() + self.edge_attrs():
-            if isinstance(self.data[attr], torch.Tensor):
-                self.data[attr] = self.data[attr].to(device)
-        if "inverse_idx" in self.data and isinstance(self.data.inverse_idx, torch.Tensor):
-            self.data.inverse_idx = self.data.inverse_idx.to(device)
+        """Move all tensors to ``device`` in place and return ``self`` (reference graph.py:273-296); deferred ones stay deferred."""
+        for key in ["edge_index", "node_sequence", *self.node_attrs(), *self.edge_attrs(), "inverse_idx"]:
+            self.data[key] = moved(self.data.peek(key), device)
         if self._csr is not None:
             self._csr = tuple(t.to(device) for t in self._csr)
         if self._csc is not None:

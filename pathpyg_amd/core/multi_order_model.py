@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 from scipy.stats import chi2
 
-from .. import _dispatch
+from .. import _dispatch, _hip
 from ..algorithms.lift_order import (
     aggregate_edge_index,
     aggregate_node_attributes,
@@ -116,7 +116,7 @@ class MultiOrderModel:
         if weight in data:
             edge_weight = data[weight]
         else:
-            edge_weight = _hip_unit()        # the reference's torch.ones(m) (:150-151) as a marker: unit weights stay unit under the "src" lift,
+            edge_weight = _hip.UNIT          # the reference's torch.ones(m) (:150-151) as a marker: unit weights stay unit under the "src" lift,
             #                                  and the weight of a merged edge is the length of its run (pp_coalesce_fill, no gather)
         first_order = torch.arange(n, device=dev).unsqueeze(1)
         chain = _LiftChain.first_order(edge_index, first_order, edge_weight, identity_nodes=True, num_first_order=n,
@@ -183,7 +183,6 @@ class MultiOrderModel:
         n = int(g1.data.num_nodes)
         dof = n - 1
         if assumption == "paths":
-            from .. import _hip
             edge_index = g1.data.edge_index
             for k in range(1, max_order + 1):
                 if k > 1:
@@ -379,25 +378,16 @@ class MultiOrderModel:
         return built
 
 
-def _hip_unit() -> str:
-    from .._hip import UNIT
-    return UNIT
-
-
 def _csr_rows(ptr: torch.Tensor, total: int) -> torch.Tensor:
     """Row id of every entry of a CSR with int32 row pointers ``ptr`` (int64 [total])."""
     n = ptr.numel() - 1
     return torch.repeat_interleave(torch.arange(n, device=ptr.device), (ptr[1:] - ptr[:-1]).long(), output_size=total)
 
 
-def _second_order_fused(g: TemporalGraph, delta, weight: str, cached: bool):
-    """``from_temporal_graph(g, delta, max_order=2)`` on the fused order-2 builder (``_hip.debruijn2`` -> ``pp_debruijn2_count / _fill``): ONE pass
-    over the stream yields both layers as CSR plans — no event graph, no ``[E_2, 2]`` instance tensors, one read-back.  The reference's layer
-    tensors (reference multi_order_model.py:153-181: ``edge_index``, ``edge_weight``, ``node_sequence``, ``inverse_idx`` of both layers) are
-    :class:`~pathpyg_amd.data.Lazy` views of those plans, identical to what the generic kernels produce, made when somebody reads them.
-    ``None``: the builder does not apply (host-resident stream, a weight attribute that is not float32, an unsorted stream) or is not the one to use
-    (a contact-shaped stream, ``_hip.debruijn2_wanted``)."""
-    from .. import _hip
+def _fast_stream(g: TemporalGraph, weight: str):
+    """``(ei, time, w, n, m)`` of a stream the fast builders (:func:`_second_order_fused`, :func:`_multi_order_fused`) take: edge index and
+    timestamps on the device, the weight attribute absent (``w`` None) or float32 on the device, n > 0 nodes, m > 0 events, sorted by time
+    (unsorted: one cheap kernel here instead of a builder's whole count pass); else ``None``."""
     data = g.data
     ei = _dispatch.plain(data.edge_index)
     time = data.time
@@ -408,55 +398,89 @@ def _second_order_fused(g: TemporalGraph, delta, weight: str, cached: bool):
         w = data[weight]
         if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or not w.is_cuda:
             return None
-    n, m_events = int(data.num_nodes), int(ei.size(1))
-    if n == 0 or m_events == 0 or not _hip.debruijn2_wanted(m_events, n):
+    n, m = int(data.num_nodes), int(ei.size(1))
+    if n == 0 or m == 0 or not data.is_sorted_by_time():
         return None
-    if not data.is_sorted_by_time():          # (unsorted: one cheap kernel instead of the builder's whole count pass)
+    return ei, time, w, n, m
+
+
+def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, weight2=None, inverse_high=None) -> dict:
+    """The layers a fast build keeps (all, or with ``cached=False`` the top one) as :class:`~pathpyg_amd.data.Lazy` views of its source-major
+    CSR arrays, ``csr[k - 1]`` = layer k (:class:`~pathpyg_amd._hip.MultiOrderLayer`), identical to what the generic kernels produce, made when
+    somebody reads them (reference multi_order_model.py:153-191): ``edge_index`` = (row of every CSR entry, column); ``node_sequence`` of layer 1
+    = ``arange(n)``, of layer k the sequence of the entry's row in layer k-1 followed by the entry's last node (De Bruijn property: the nodes of
+    layer k ARE the edges of layer k-1; for layer 2 that is layer 1's edge itself); ``inverse_idx`` of layer 1 = ``arange(n)``, of layer 2 the
+    merged first-order edge of every event, from layer 3 on ``inverse_high(k)``.  ``weight2(edge_index)``: layer 2's merged weights, for a
+    builder that does not keep them in the layer's edge order."""
+    # (the makers capture CSR arrays, plans and other Lazy objects, never the Data bags that hold them: a bag -> Lazy -> closure -> bag cycle would
+    #  keep ~4 GB of plans per model alive until the cyclic collector runs — measured: 14.0 -> 20.8 ms per API step from the 11th step on)
+    n, dev = csr[0].n_nodes, ei.device
+    layers = {}
+    index = seq = None
+    for k, b in enumerate(csr, start=1):
+        prev_index, prev_seq = index, seq
+        index = Lazy(lambda b=b: torch.stack((_csr_rows(b.row_ptr, b.n_edges), b.col.long())), (2, b.n_edges))
+        weight = b.weight
+        if k == 1:
+            seq = Lazy(lambda: torch.arange(n, device=dev).unsqueeze(1), (n, 1))
+            inverse = Lazy(lambda: torch.arange(n, device=dev), (n,))
+        elif k == 2:
+            seq = Lazy(lambda first=prev_index: first.resolve().t().contiguous(), (b.n_nodes, 2))
+
+            def inverse_of(first=prev_index):
+                # order-2 node of every event = its merged first-order edge (lift_order.py:133 on the [m, 2] instance rows)
+                e1 = first.resolve()
+                return torch.searchsorted(e1[0] * n + e1[1], ei[0] * n + ei[1])
+
+            inverse = Lazy(inverse_of, (csr[0].n_instances,))
+            if weight2 is not None:
+                weight = Lazy(lambda index=index: weight2(index.resolve()), (b.n_edges,))
+        else:
+            def seq_of(prev_index=prev_index, prev_seq=prev_seq, last=csr[k - 2].last):
+                # node u of layer k = edge u of layer k-1: the sequence of that edge's source node, then the edge's last node
+                return _dispatch.gather_concat(prev_seq.resolve(), prev_index.resolve()[0].contiguous(), last.long())
+
+            seq = Lazy(seq_of, (b.n_nodes, k))
+            inverse = Lazy(lambda k=k: inverse_high(k), (csr[k - 2].n_instances,))
+        if cached or k == len(csr):
+            d = Data(edge_index=index, num_nodes=b.n_nodes, node_sequence=seq, edge_weight=weight, inverse_idx=inverse)
+            layers[k] = Graph._from_parts(d, g.mapping if k == 1 else IndexMap.from_node_sequence(g.mapping, seq))
+            if k == 2:
+                layers[k]._nodes_are_fo_edges = True
+    return layers
+
+
+def _second_order_fused(g: TemporalGraph, delta, weight: str, cached: bool):
+    """``from_temporal_graph(g, delta, max_order=2)`` on the fused order-2 builder (``_hip.debruijn2`` -> ``pp_debruijn2_count / _fill``): ONE pass
+    over the stream yields both layers as CSR plans — no event graph, no ``[E_2, 2]`` instance tensors, one read-back.  The reference's layer
+    tensors are deferred views of those plans (:func:`_csr_layers`).
+    ``None``: the builder does not apply (see :func:`_fast_stream`) or is not the one to use (a contact-shaped stream, ``_hip.debruijn2_wanted``)."""
+    stream = _fast_stream(g, weight)
+    if stream is None:
+        return None
+    ei, time, w, n, m = stream
+    if not _hip.debruijn2_wanted(m, n):
         return None
     built = _hip.debruijn2(ei, time, n, delta, w, want_weights=True, unsorted_ok=True)
     if built is None:
         return None
-    dev = ei.device
     fo, ho = built.fo, built.ho
     u2, a2 = int(built.sizes["U2"]), int(built.sizes["A2"])
-
-    # (the makers below capture plans and other Lazy objects, never the Data bags that hold them: a bag -> Lazy -> closure -> bag cycle would keep
-    #  ~4 GB of plans per model alive until the cyclic collector runs — measured: 14.0 -> 20.8 ms per API step from the 11th step on)
-    ei1 = Lazy(lambda: torch.stack((_csr_rows(fo.bwd_ptr, u2), fo.bwd_idx.long())), (2, u2))
-    lazy1 = {"edge_index": ei1,
-             "node_sequence": Lazy(lambda: torch.arange(n, device=dev).unsqueeze(1), (n, 1)),
-             "inverse_idx": Lazy(lambda: torch.arange(n, device=dev), (n,))}
-    d1 = Data(edge_index=ei1, num_nodes=n, node_sequence=lazy1["node_sequence"], edge_weight=built.fo_weight, inverse_idx=lazy1["inverse_idx"])
-    g1 = Graph._from_parts(d1, g.mapping)
-    ei2 = Lazy(lambda: torch.stack((_csr_rows(ho.bwd_ptr, a2), ho.bwd_idx.long())), (2, a2))
     fwd_weight = built.ho_fwd_weight
 
-    def weights2():
+    def weights2(e2):
         # the builder keeps the merged weights in destination-major order (contiguous stores); the layer lists its edges source-major
-        e2 = ei2.resolve()
         key_fwd = _csr_rows(ho.fwd_ptr, a2) * u2 + ho.fwd_idx.long()                       # ascending: rows ascending, sources ascending inside a row
         return fwd_weight[torch.searchsorted(key_fwd, e2[1] * u2 + e2[0])]
 
-    def inverse2():
-        # order-2 node of every event = its merged first-order edge (lift_order.py:133 on the [m, 2] instance rows)
-        e1 = ei1.resolve()
-        return torch.searchsorted(e1[0] * n + e1[1], ei[0] * n + ei[1])
-
-    lazy2 = {"edge_index": ei2,
-             "node_sequence": Lazy(lambda: ei1.resolve().t().contiguous(), (u2, 2)),
-             "edge_weight": Lazy(weights2, (a2,)),
-             "inverse_idx": Lazy(inverse2, (m_events,))}
-    d2 = Data(edge_index=ei2, num_nodes=u2, node_sequence=lazy2["node_sequence"], edge_weight=lazy2["edge_weight"],
-              inverse_idx=lazy2["inverse_idx"])
-    g2 = Graph._from_parts(d2, IndexMap.from_node_sequence(g.mapping, lazy2["node_sequence"]))
-    g2._nodes_are_fo_edges = True
+    csr = [_hip.MultiOrderLayer(n_nodes=n, n_edges=u2, n_instances=m, row_ptr=fo.bwd_ptr, col=fo.bwd_idx, weight=built.fo_weight),
+           _hip.MultiOrderLayer(n_nodes=u2, n_edges=a2, n_instances=built.sizes["E2"], row_ptr=ho.bwd_ptr, col=ho.bwd_idx)]
     out = MultiOrderModel()
+    out.layers = _csr_layers(g, ei, csr, cached, weight2=weights2)
     if cached:
-        out.layers[1] = g1
-    out.layers[2] = g2
-    if cached:
-        out._pp_fused = (built, {1: (g1, {"edge_index": lazy1["edge_index"], "edge_weight": (built.fo_weight, built.fo_weight._version)}),
-                                 2: (g2, {"edge_index": lazy2["edge_index"], "edge_weight": lazy2["edge_weight"]})})
+        d1, d2 = out.layers[1].data, out.layers[2].data
+        out._pp_fused = (built, {1: (out.layers[1], {"edge_index": d1.peek("edge_index"), "edge_weight": (built.fo_weight, built.fo_weight._version)}),
+                                 2: (out.layers[2], {"edge_index": d2.peek("edge_index"), "edge_weight": d2.peek("edge_weight")})})
     out.sizes = dict(built.sizes)
     return out
 
@@ -468,7 +492,6 @@ LIFT_ONLY_ORDER2 = False     # from_temporal_graph(max_order=2) on a stream with
 def _has_large_hub(g: TemporalGraph) -> bool:
     """Whether some node of a device-resident stream has ``LARGE_HUB_EVENTS`` or more in- or out-events (two histograms and one read-back, kept
     on the graph object for the tensors they were taken from)."""
-    from .. import _hip
     ei = _dispatch.plain(g.data.edge_index)
     if ei is None or not ei.is_cuda or ei.numel() == 0 or ei.size(1) < LARGE_HUB_EVENTS:
         return False
@@ -484,27 +507,15 @@ def _has_large_hub(g: TemporalGraph) -> bool:
 
 def _multi_order_fused(g: TemporalGraph, delta, max_order: int, weight: str, cached: bool, event_graph=None):
     """``from_temporal_graph(g, delta, max_order >= 3)`` level by level (``_hip.multi_order_temporal`` -> ``pp_multiorder_prepare`` / ``_step``): every
-    layer comes out as source-major CSR with merged weights; the reference's layer tensors (reference multi_order_model.py:153-191) are
-    :class:`~pathpyg_amd.data.Lazy` views — ``edge_index`` = (row of every CSR entry, column), ``node_sequence`` of layer k = the sequence of the
-    entry's row in layer k-1 followed by the entry's last node (De Bruijn property: the nodes of layer k ARE the edges of layer k-1),
-    ``inverse_idx`` of the layers from 3 on through the generic kernels (it numbers the reference's instance graph, which this builder never makes).
+    layer comes out as source-major CSR with merged weights, the reference's layer tensors are deferred views of it (:func:`_csr_layers`), the
+    ``inverse_idx`` of the layers from 3 on comes from the generic kernels (:func:`_generic_inverses`).
     ``event_graph``: a given ``lift_order_temporal(g, delta)`` — its edges are the continuation windows (``pp_multiorder_prepare_graph``).
-    ``None``: the builder does not apply (host-resident or unsorted stream, a weight attribute that is not float32, a layer without edges, a node
-    sequence with more than 4096 continuations, 2^31 instances, an event graph that is not sorted by source)."""
-    from .. import _hip
-    data = g.data
-    ei = _dispatch.plain(data.edge_index)
-    time = data.time
-    if ei is None or time is None or not ei.is_cuda or not time.is_cuda:
+    ``None``: the builder does not apply (see :func:`_fast_stream`; a layer without edges, a node sequence with more than 4096 continuations,
+    2^31 instances, an event graph that is not sorted by source)."""
+    stream = _fast_stream(g, weight)
+    if stream is None:
         return None
-    w = None
-    if weight in data:
-        w = data[weight]
-        if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or not w.is_cuda:
-            return None
-    n, m_events = int(data.num_nodes), int(ei.size(1))
-    if n == 0 or m_events == 0 or not data.is_sorted_by_time():
-        return None
+    ei, time, w, n, m = stream
     if event_graph is not None:
         event_graph = _dispatch.plain(event_graph)
         if not isinstance(event_graph, torch.Tensor) or not event_graph.is_cuda or event_graph.dim() != 2 or event_graph.size(0) != 2:
@@ -512,46 +523,25 @@ def _multi_order_fused(g: TemporalGraph, delta, max_order: int, weight: str, cac
     built = _hip.multi_order_temporal(ei, time, n, delta, w, max_order, event_graph=event_graph)
     if built is None:
         return None
-    dev = ei.device
     out = MultiOrderModel()
-    out.sizes = {"m": m_events, "N": n, "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in built]}
-    prev_index = prev_seq = None
-    for k, b in enumerate(built, start=1):
-        keep = cached or k == max_order
-
-        def index_of(b=b):
-            return torch.stack((_csr_rows(b.row_ptr, b.n_edges), b.col.long()))
-
-        index = Lazy(index_of, (2, b.n_edges))
-        if k == 1:
-            seq = Lazy(lambda: torch.arange(n, device=dev).unsqueeze(1), (n, 1))
-            inverse = Lazy(lambda: torch.arange(n, device=dev), (n,))
-        else:
-            def seq_of(prev_index=prev_index, prev_seq=prev_seq, last=built[k - 2].last):
-                # node u of layer k = edge u of layer k-1: the sequence of that edge's source node, then the edge's last node
-                return _dispatch.gather_concat(prev_seq.resolve(), prev_index.resolve()[0].contiguous(), last.long())
-
-            seq = Lazy(seq_of, (b.n_nodes, k))
-            if k == 2:
-                def inverse_of(first=prev_index):
-                    # order-2 node of every event = its merged first-order edge (lift_order.py:133 on the [m, 2] instance rows)
-                    e1 = first.resolve()
-                    return torch.searchsorted(e1[0] * n + e1[1], ei[0] * n + ei[1])
-            else:
-                def inverse_of(k=k):
-                    # the reference numbers the order-k INSTANCES (edges of the order-(k-1) instance graph, lexicographic): only the generic
-                    # kernels make that graph
-                    return MultiOrderModel._from_temporal_graph_generic(g, delta, k, weight, False, event_graph).layers[k].data.inverse_idx
-
-            inverse = Lazy(inverse_of, (built[k - 2].n_instances,))
-        if keep:
-            d = Data(edge_index=index, num_nodes=b.n_nodes, node_sequence=seq, edge_weight=b.weight, inverse_idx=inverse)
-            mapping = g.mapping if k == 1 else IndexMap.from_node_sequence(g.mapping, seq)
-            out.layers[k] = Graph._from_parts(d, mapping)
-            if k == 2:
-                out.layers[k]._nodes_are_fo_edges = True
-        prev_index, prev_seq = index, seq
+    out.sizes = {"m": m, "N": n, "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in built]}
+    out.layers = _csr_layers(g, ei, built, cached, inverse_high=_generic_inverses(g, delta, max_order, weight, cached, event_graph))
     return out
+
+
+def _generic_inverses(g: TemporalGraph, delta, max_order: int, weight: str, cached: bool, event_graph):
+    """``k -> inverse_idx`` of the layers from 3 on of a level-by-level model.  It numbers the reference's order-k INSTANCES (edges of the
+    order-(k-1) instance graph, lexicographic), which only the generic kernels make: ONE generic build of the same layers, on first use,
+    serves every layer of the model (one per layer would run K - 2 of them); only its inverse maps are kept."""
+    kept = {}
+
+    def inverse_of(k):
+        if not kept:
+            model = MultiOrderModel._from_temporal_graph_generic(g, delta, max_order, weight, cached, event_graph)
+            kept.update((j, layer.data.inverse_idx) for j, layer in model.layers.items() if j >= 3)
+        return kept[k]
+
+    return inverse_of
 
 
 class _LiftChain:
@@ -660,7 +650,6 @@ class _LiftChain:
 
 def _dispatch_degree(index: torch.Tensor, num_nodes: int) -> torch.Tensor:
     """Out-degree histogram as a float tensor on the input's device (PyG ``degree``, multi_order_model.py:220)."""
-    from .. import _hip
     dev = _dispatch.compute_device(index)
     deg = _hip.degree(_dispatch.plain(index).to(dev).contiguous(), num_nodes)
     return deg.to(torch.float32).to(index.device)

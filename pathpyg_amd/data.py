@@ -55,6 +55,16 @@ def _made(value) -> "Lazy":
     return out
 
 
+def moved(value: Any, device) -> Any:
+    """``value`` on ``device``: a tensor through ``.to``, a :class:`Lazy` as a deferred move (it stays deferred: moving a layer or a bundle must not
+    materialise every [2, A2] index), anything else as it is."""
+    if isinstance(value, torch.Tensor):
+        return value.to(device)
+    if isinstance(value, Lazy):
+        return value.mapped(lambda t: t.to(device))
+    return value
+
+
 class Data:
     def __init__(self, **attrs: Any) -> None:
         object.__setattr__(self, "_store", {})
@@ -183,12 +193,8 @@ class Data:
 
     # ------------------------------------------------------------ device / time helpers
     def to(self, device) -> "Data":
-        # (deferred tensors stay deferred: `bundle.to(dev)` on a fused model must not materialise every [2, A2] index)
         for key, value in list(self._store.items()):
-            if isinstance(value, torch.Tensor):
-                self._store[key] = value.to(device)
-            elif isinstance(value, Lazy):
-                self._store[key] = value.mapped(lambda t, device=device: t.to(device))
+            self._store[key] = moved(value, device)
         return self
 
     def clone(self) -> "Data":

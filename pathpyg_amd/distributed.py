@@ -20,7 +20,7 @@ import math
 import torch
 import torch.distributed as dist
 
-from . import _dispatch
+from . import _dispatch, _hip
 
 
 def _world(group=None) -> tuple[int, int]:
@@ -662,16 +662,6 @@ def _even_cuts(num_nodes: int, world: int) -> list[int]:
     return [(num_nodes * r) // world for r in range(world + 1)]
 
 
-def _debruijn2_wanted(m: int, n: int) -> bool:
-    from ._hip import debruijn2_wanted
-    return debruijn2_wanted(m, n)
-
-
-def _hip_unit():
-    from ._hip import UNIT
-    return UNIT
-
-
 def _ops_default(ops):
     if ops is not None:
         return ops
@@ -1016,7 +1006,7 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
     n, m = int(data.num_nodes), int(ei.size(1))
     unit_weights = weight not in data
     fused = getattr(ops, "debruijn2", None) if FUSED_BUILDER else None
-    if fused is not None and m > 0 and n > 0 and (unit_weights or data[weight].dtype == torch.float32) and (FUSED_BUILDER == "always" or _debruijn2_wanted(m, n)):
+    if fused is not None and m > 0 and n > 0 and (unit_weights or data[weight].dtype == torch.float32) and (FUSED_BUILDER == "always" or _hip.debruijn2_wanted(m, n)):
         built = fused(ei, data.time, n, delta, None if unit_weights else data[weight])
         if built is not None:              # (None: a hub node — the generic path below)
             from .nn.sharded import GraphShard
@@ -1031,7 +1021,7 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
                               sizes={"m": m, "N": n, "E2": built.sizes["E2"], "E2_local": built.sizes["E2"], "U2": n_ho, "A1": built.sizes["A1"],
                                      "A2": built.sizes["A2"], "A2_local": built.sizes["A2"], "fo_cuts": [0, n], "ho_cuts": [0, n_ho], "fo_halo": 0,
                                      "ho_halo": 0, "builder": "fused"})
-    w = _hip_unit() if unit_weights else data[weight]                       # (unit weights: merged weight = run length, no ones vector, no gather)
+    w = _hip.UNIT if unit_weights else data[weight]                         # (unit weights: merged weight = run length, no ones vector, no gather)
     # layer 1 and the lift of the same stream are independent: their count phases are queued together, their sizes cost ONE read-back
     (fo, fo_w, inv1), local = ops.coalesce_and_lift((ei, w, n, "sum", None, True), (ei, data.time.contiguous(), n, delta, m, 0))
     n_ho = int(fo.size(1))
@@ -1214,7 +1204,6 @@ def _own_rows_buffer(source, lo: int, hi: int, row_of: torch.Tensor, n_halo: int
     buf = torch.empty((n_own + n_halo, part.size(1)), dtype=part.dtype, device=part.device)
     if n_own:
         if part.is_cuda and part.dtype == torch.float32 and part.size(1) % 4 == 0:
-            from . import _hip
             _hip.gather_rows(part.contiguous(), row_of, out=buf[:n_own])
         else:
             torch.index_select(part, 0, row_of.to(torch.int64), out=buf[:n_own])
@@ -1317,7 +1306,7 @@ def _build_partitioned(g, delta, x, x_h, y, comm: Comm, ops, weight: str):
     n_fo_own = hi_n - lo_n
     m_l1 = int(ss.ei_l1.size(1))
     # ---- 1. layer 1 on the events that start in my node range  +  2. the edge-range lift (count phases queued together: one read-back)
-    w_r = _hip_unit() if unit_weights else ss.w_l1
+    w_r = _hip.UNIT if unit_weights else ss.w_l1
     (fo_r, fo_w_r, inv_r), local = ops.coalesce_and_lift((ss.ei_l1, w_r, n, "sum", None, True),
                                                          (ss.ei_lift, ss.time_lift, n, delta, ss.n_own_lift, 0))       # (ids relative to my slice)
     n_ho_own = int(fo_r.size(1))
@@ -1355,7 +1344,7 @@ def _build_partitioned(g, delta, x, x_h, y, comm: Comm, ops, weight: str):
     pairs = torch.stack((u, v), dim=1).to(torch.int32).index_select(0, p_order)
     pairs_in = comm.exchange_rows(pairs, p_send, p_recv)
     if unit_weights:
-        w_in = _hip_unit()
+        w_in = _hip.UNIT
     else:
         w_in = comm.exchange_rows(ss.w_lift.index_select(0, local[0]).index_select(0, p_order), p_send, p_recv)     # weight of the source event
     own_ids = torch.arange(lo_h, hi_h, **i64)

@@ -160,6 +160,40 @@ def test_large_streams_equal_the_generic_kernels(pp, shape):
         assert torch.equal(fast.layers[3].data.inverse_idx, slow.layers[3].data.inverse_idx)      # (made by the generic kernels on demand)
 
 
+def test_moved_layers_stay_deferred_and_share_one_generic_build(pp, monkeypatch):
+    # Graph.to moves deferred tensors as deferred moves: .to() on a level-by-level model runs no generic build; the inverse_idx of all layers
+    # from 3 on then come out of ONE generic build (not one per layer), and every tensor read is the generic kernels'
+    from pathpyg_amd.core import multi_order_model as mm
+    ei, t, w, n, delta = _stream("hubs", 5)
+    g = pp.TemporalGraph(pp.Data(edge_index=ei.to(DEV), time=t.to(DEV), num_nodes=n, edge_weight=w.to(DEV)))
+    slow = _generic(pp, g, delta, 5)
+    fast = pp.MultiOrderModel.from_temporal_graph(g, delta=delta, max_order=5, cached=True)
+    assert _level_by_level(fast) and sorted(fast.layers) == [1, 2, 3, 4, 5]
+    real = mm.MultiOrderModel._from_temporal_graph_generic
+    calls = []
+
+    def no_generic(*args):
+        raise AssertionError("Graph.to ran a generic build")
+
+    monkeypatch.setattr(mm.MultiOrderModel, "_from_temporal_graph_generic", staticmethod(no_generic))
+    assert fast.to(DEV) is fast
+    assert all(isinstance(fast.layers[k].data.peek("inverse_idx"), pp.data.Lazy) for k in range(1, 6))
+    for k in range(1, 6):
+        a, b = fast.layers[k].data, slow.layers[k].data
+        for key in ("edge_index", "edge_weight", "node_sequence"):
+            assert torch.equal(a[key], b[key]), (k, key)
+
+    def counted(*args):
+        calls.append(args)
+        return real(*args)
+
+    monkeypatch.setattr(mm.MultiOrderModel, "_from_temporal_graph_generic", staticmethod(counted))
+    for k in (3, 4, 5):
+        assert torch.equal(fast.layers[k].data.inverse_idx, slow.layers[k].data.inverse_idx), k
+    assert len(calls) == 1
+    assert torch.equal(fast.layers[2].data.inverse_idx, slow.layers[2].data.inverse_idx)
+
+
 def test_dbgnn_bundle_of_a_higher_layer(pp):
     # to_dbgnn_data(max_order=3) on layers that are CSR views: the bundle's tensors are the oracle's
     from oracle import model as om

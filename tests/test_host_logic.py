@@ -72,6 +72,27 @@ def test_compute_entry_points_fail_loudly_without_gpu():
             pp.nn.optim.Adam([w], **bad)
 
 
+def test_event_stream_normaliser():
+    # the checks temporal_lift, debruijn2, multi_order_temporal and debruijn2_part_count share: device-agnostic, so plain CPU tensors here
+    ei = torch.tensor([[0, 1, 2], [1, 2, 0]])
+    time, w = _hip._event_stream(ei, torch.tensor([3, 1, 2], dtype=torch.int16))
+    assert time.dtype == torch.int64 and time.tolist() == [3, 1, 2] and w is None
+    w32 = torch.arange(6, dtype=torch.float32)[::2]
+    time, w = _hip._event_stream(ei, torch.tensor([0.5, 1.0, 2.0], dtype=torch.float64), w32)
+    assert time.dtype == torch.float64 and w.is_contiguous() and torch.equal(w, w32)
+    with pytest.raises(TypeError, match="int64 or float64"):
+        _hip._event_stream(ei, torch.tensor([1.0, 2.0, 3.0]), w32)
+    with pytest.raises(ValueError, match="number of events"):
+        _hip._event_stream(ei, torch.tensor([1, 2]))
+    assert _hip._event_stream(ei, torch.tensor([1, 2, 3]), torch.ones(3, dtype=torch.float64)) is None      # does not apply
+    assert _hip._event_stream(ei, torch.tensor([1, 2, 3]), torch.ones(2)) is None
+    # the callers look at the device first: a host stream is the "no CPU path" error, not a dtype error
+    for call in (lambda t: _hip.temporal_lift(ei, t, 3, 1), lambda t: _hip.debruijn2(ei, t, 3, 1),
+                 lambda t: _hip.multi_order_temporal(ei, t, 3, 1, None, 3)):
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            call(torch.tensor([1.0, 2.0, 3.0]))
+
+
 def test_delta_resolution_follows_torch_promotion():
     i64, f64 = torch.int64, torch.float64
     assert _hip.resolve_delta(i64, 5) == (_hip.DELTA_I64, 5, 0.0)
