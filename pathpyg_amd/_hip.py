@@ -774,7 +774,8 @@ def debruijn2_wanted(m: int, num_nodes: int) -> bool:
     in-events x out-events of the middle node — and is built for nodes with tens of events per side (hubs are chunked).  On a contact-shaped
     stream (tens of nodes, 10^4 events per node and side: 96 nodes / 2 * 10^6 events) every node is a hub and the per-node scans cost 1.9 ms where
     lift -> coalesce -> coalesce -> plans takes 1.0 ms (``hub_streams`` in the bench line): from ``DENSE_EVENTS_PER_NODE`` events per node on average
-    the callers that choose (``MultiOrderModel.from_temporal_graph``, ``distributed.build_dbgnn_shard``) take the generic kernels."""
+    the callers that choose (``MultiOrderModel.from_temporal_graph``, ``distributed.build_dbgnn_shard`` at world size 1) take the generic kernels.
+    At world size > 1 ``build_dbgnn_shard`` does not ask: it always tries the node-range builder first."""
     return m <= DENSE_EVENTS_PER_NODE * max(int(num_nodes), 1)
 
 

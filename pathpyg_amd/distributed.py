@@ -1,17 +1,12 @@
-"""Multi-GPU sharding of the lift: one process per GPU, ``torch.distributed`` (backend ``nccl`` = RCCL on ROCm).
+"""Multi-GPU sharding: one process per GPU, ``torch.distributed`` (backend ``nccl`` = RCCL on ROCm).  Three parts:
 
-The reference is single-process; this is new design following SURVEY §8(e):
-
-* temporal lift — **edge-range shards with a forward halo, no data exchange**.  Events are time-sorted, so the
-  continuations of the source events ``[lo, hi)`` all lie in ``[lo+1, halo_end)`` with
-  ``halo_end = first event with t > t[hi-1] + delta``.  Rank ``r`` lifts its slice ``[lo_r, halo_end_r)`` with only
-  the first ``hi_r - lo_r`` events acting as sources (``n_own``) and global ids restored by ``id_offset``; the
-  concatenation of the per-rank results in rank order IS the global lexicographic result.  The only collective is
-  one all-gather of the per-rank pair counts (8 bytes per rank) for global output offsets.
-* ranges are balanced on OUTPUT size when a per-event count estimate is supplied, else on event count.
-
-Everything below the collectives runs through ``pathpyg_amd._dispatch`` (HIP kernels); tests exercise the
-planner and the collectives on CPU with the ``gloo`` backend by substituting the local lift.
+* transport — :class:`Comm`: the collectives, byte counters and a per-collective log; host-staged for gloo (tests), and R ranks as
+  threads of one process on one GPU (:class:`ThreadWorld`, :func:`run_thread_world`).  Every collective of this module goes through it;
+* stream primitives — edge-range shards of the lifts with a forward halo and no data exchange (:func:`lift_order_temporal_sharded`,
+  :func:`lift_order_edge_index_sharded`), key-range sharded aggregation (:func:`coalesce_sharded`, :func:`unique_pairs_sharded`,
+  :func:`second_order_layer_sharded`), :func:`all_reduce_gradients`.  Device work goes through ``ops`` (default: ``_dispatch``);
+* the partitioned DBGNN builders — :func:`build_dbgnn_shard` (node-range split on the node-by-node order-2 builder, else the edge-range
+  split of :func:`_build_partitioned`), graph shards with their halo exchanges, :class:`~pathpyg_amd.nn.sharded.ShardedDBGNN`.
 """
 from __future__ import annotations
 
@@ -21,12 +16,11 @@ import torch
 import torch.distributed as dist
 
 from . import _dispatch, _hip
+from .nn.dbgnn import _stamp, _stamp_matches
 
 
-def _world(group=None) -> tuple[int, int]:
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_rank(group), dist.get_world_size(group)
-    return 0, 1
+def _even_cuts(num_nodes: int, world: int) -> list[int]:
+    return [(num_nodes * r) // world for r in range(world + 1)]
 
 
 def event_ranges(num_events: int, world_size: int, weights: torch.Tensor | None = None) -> list[tuple[int, int]]:
@@ -37,7 +31,7 @@ def event_ranges(num_events: int, world_size: int, weights: torch.Tensor | None 
     if world_size < 1:
         raise ValueError("world_size must be >= 1")
     if weights is None or num_events == 0:
-        cuts = [(num_events * r) // world_size for r in range(world_size + 1)]
+        cuts = _even_cuts(num_events, world_size)
     else:
         if weights.numel() != num_events:
             raise ValueError("weights must hold one value per event")
@@ -58,94 +52,77 @@ def halo_end(time: torch.Tensor, hi: int, delta) -> int:
     m = int(time.numel())
     if hi <= 0 or hi >= m:
         return m if hi > 0 else 0
-    # one searchsorted on the device and ONE read-back (this used to be a host bisection: ~log2(m) scalar reads per step and rank)
-    delta_t = delta.to(time.device) if isinstance(delta, torch.Tensor) else torch.as_tensor(delta, device=time.device)
-    thr = time[hi - 1] + delta_t                                     # promoted like the reference's comparison
-    if thr.dtype != time.dtype and not time.dtype.is_floating_point:
-        # a float threshold over integer times: float(t) <= thr admits no integer above ceil(thr) + one rounding step of the float type
-        t64 = thr.double()
-        step = t64.abs() * (2.0 ** -23 if thr.dtype == torch.float32 else 2.0 ** -52) + 1.0
-        bound = torch.ceil(t64 + step).clamp(max=float(2 ** 62)).to(torch.int64)
-    else:
-        bound = thr.to(time.dtype)
-    return hi + int(torch.searchsorted(time[hi:], bound, right=True).item())
+    # a 0-d range end: the threshold is promoted like the reference's scalar comparison; one read-back
+    return int(_window_ends(time, torch.full((), hi, dtype=torch.int64, device=time.device), delta).item())
 
 
-def lift_order_temporal_sharded(g, delta=1, group=None, weights: torch.Tensor | None = None):
-    """This rank's part of ``lift_order_temporal(g, delta)`` for a stream replicated on every rank.
+def lift_order_temporal_sharded(g, delta=1, group=None, weights: torch.Tensor | None = None, *, comm: "Comm | None" = None, ops=None):
+    """This rank's part of ``lift_order_temporal(g, delta)`` for a stream replicated on every rank: rank r lifts its source-event range
+    ``[lo, hi)`` plus the forward halo ``[hi, halo_end)`` with ``n_own = hi - lo`` sources and global ids restored by ``id_offset``; the
+    only collective is the all-gather of the per-rank pair counts.  ``comm`` defaults to ``Comm(group)``, ``ops`` to ``_dispatch``.
 
     Returns ``(local_index [2, E_r] int64 with GLOBAL event ids, global_offset, global_total)``: rank ``r``'s block
     occupies columns ``[global_offset, global_offset + E_r)`` of the full lexicographic result."""
-    rank, world = _world(group)
+    comm = Comm(group) if comm is None else comm
+    ops = _dispatch if ops is None else ops
     data = g.data
     m = int(data.edge_index.size(1))
-    lo, hi = event_ranges(m, world, weights)[rank]
+    lo, hi = event_ranges(m, comm.world, weights)[comm.rank]
     end = halo_end(data.time, hi, delta) if hi > lo else lo
     ei = _dispatch.plain(data.edge_index)[:, lo:end].contiguous()
     t = data.time[lo:end].contiguous()
-    local = _dispatch.temporal_lift(ei, t, int(data.num_nodes), delta, n_own=hi - lo, id_offset=lo)
-    counts = torch.tensor([local.size(1)], dtype=torch.int64, device=local.device)
-    if world > 1:
-        gathered = [torch.zeros_like(counts) for _ in range(world)]
-        dist.all_gather(gathered, counts, group=group)
-        sizes = [int(c.item()) for c in gathered]
-    else:
-        sizes = [int(counts.item())]
-    return local, sum(sizes[:rank]), sum(sizes)
+    local = ops.temporal_lift(ei, t, int(data.num_nodes), delta, n_own=hi - lo, id_offset=lo)
+    sizes = [row[0] for row in comm.all_gather_ints([local.size(1)], local.device)]
+    return local, sum(sizes[:comm.rank]), sum(sizes)
 
 
-def lift_order_edge_index_sharded(edge_index: torch.Tensor, num_nodes: int, group=None, weights: torch.Tensor | None = None):
+def lift_order_edge_index_sharded(edge_index: torch.Tensor, num_nodes: int, group=None, weights: torch.Tensor | None = None, *,
+                                  comm: "Comm | None" = None, ops=None):
     """Edge-range sharded line-graph lift of a source-sorted edge list replicated on every rank: rank r expands
     the edges ``[lo_r, hi_r)``; out-degrees and row pointers are derived locally from the replicated list, so the only collective
-    is the all-gather of the per-rank pair counts.  Returns ``(local [2, E'_r] with global ids, ranges, total E')``; the rank-order
+    is the all-reduce of the pair count.  Returns ``(local [2, E'_r] with global ids, ranges, total E')``; the rank-order
     concatenation of the blocks is the single-process result."""
-    rank, world = _world(group)
+    comm = Comm(group) if comm is None else comm
+    ops = _dispatch if ops is None else ops
     ei = _dispatch.plain(edge_index)
-    ranges = event_ranges(ei.size(1), world, weights)
-    lo, hi = ranges[rank]
-    local = _dispatch.linegraph_lift(ei, num_nodes, (lo, hi))
-    total = local.size(1)
-    if world > 1:
-        counts = torch.tensor([total], dtype=torch.int64, device=local.device)
-        dist.all_reduce(counts, group=group)
-        total = int(counts.item())
-    return local, ranges, total
+    ranges = event_ranges(ei.size(1), comm.world, weights)
+    local = ops.linegraph_lift(ei, num_nodes, ranges[comm.rank])
+    total = comm.all_reduce_(torch.tensor([local.size(1)], dtype=torch.int64, device=local.device))
+    return local, ranges, int(total.item())
 
 
-def gather_lifted(local: torch.Tensor, group=None) -> torch.Tensor:
-    """Concatenate the per-rank blocks (rank order) on every rank — for tests and small graphs only."""
-    rank, world = _world(group)
-    if world == 1:
+def _gather_columns(local: torch.Tensor, comm: "Comm") -> torch.Tensor:
+    """Concatenate every rank's ``[2, k_r]`` block in rank order on every rank: the sizes, then the blocks padded to the largest."""
+    if comm.world == 1:
         return local
-    sizes = [torch.zeros(1, dtype=torch.int64, device=local.device) for _ in range(world)]
-    dist.all_gather(sizes, torch.tensor([local.size(1)], dtype=torch.int64, device=local.device), group=group)
-    cap = max(int(s.item()) for s in sizes)
-    padded = torch.zeros((2, cap), dtype=torch.int64, device=local.device)
+    sizes = [row[0] for row in comm.all_gather_ints([local.size(1)], local.device)]
+    cap = max(sizes)
+    padded = local.new_zeros((2, cap))
     padded[:, : local.size(1)] = local
-    parts = [torch.zeros_like(padded) for _ in range(world)]
-    dist.all_gather(parts, padded, group=group)
-    return torch.cat([p[:, : int(s.item())] for p, s in zip(parts, sizes)], dim=1)
+    parts = comm.all_gather_rows(padded).view(comm.world, 2, cap)
+    return torch.cat([parts[r, :, : sizes[r]] for r in range(comm.world)], dim=1)
+
+
+def gather_lifted(local: torch.Tensor, group=None, *, comm: "Comm | None" = None) -> torch.Tensor:
+    """Concatenate the per-rank blocks (rank order) on every rank — for tests and small graphs only."""
+    return _gather_columns(local, Comm(group) if comm is None else comm)
 
 
 def all_reduce_gradients(module: torch.nn.Module, group=None, average: bool = True, comm: "Comm | None" = None,
                          inplace_views: bool = False) -> None:
-    """Sum (``average=False``) or average the (small) DBGNN weight gradients across ranks in ONE flattened all-reduce
-    (latency-bound: ~20 k floats; per-tensor calls would pay the xGMI launch latency 14 times).  ``comm``: count the bytes on (and take
-    turns through) this :class:`Comm`.  The reduced values are copied back into the existing ``.grad`` tensors (references taken before the
-    call — clipping lists, hooks — see them).  ``inplace_views=True`` skips that copy: every ``.grad`` is REBOUND to a view of the one flat
-    buffer (earlier references keep the unreduced values, and any surviving view keeps the whole buffer alive) — for loops that only hand the
-    gradients to the optimizer (bench.py)."""
-    _, world = _world(group) if comm is None else (comm.rank, comm.world)
+    """Sum (``average=False``) or average the (small) DBGNN weight gradients across ranks in ONE flattened all-reduce through ``comm``
+    (latency-bound: ~20 k floats; per-tensor calls would pay the xGMI launch latency 14 times).  The reduced values are copied back into
+    the existing ``.grad`` tensors (references taken before the call — clipping lists, hooks — see them).  ``inplace_views=True`` skips
+    that copy: every ``.grad`` is REBOUND to a view of the one flat buffer (earlier references keep the unreduced values, and any surviving
+    view keeps the whole buffer alive) — for loops that only hand the gradients to the optimizer (bench.py).  ``comm`` defaults to
+    ``Comm(group)``."""
+    comm = Comm(group) if comm is None else comm
     grads = [p.grad for p in module.parameters() if p.grad is not None]
-    if world == 1 or not grads:
+    if comm.world == 1 or not grads:
         return
-    flat = torch.cat([g.reshape(-1) for g in grads])
-    if comm is not None:
-        comm.all_reduce_(flat)
-    else:
-        dist.all_reduce(flat, group=group)
+    flat = comm.all_reduce_(torch.cat([g.reshape(-1) for g in grads]))
     if average:
-        flat /= world
+        flat /= comm.world
     at = 0
     for p in module.parameters():
         if p.grad is None:
@@ -159,9 +136,9 @@ def all_reduce_gradients(module: torch.nn.Module, group=None, average: bool = Tr
 
 
 # =====================================================================================================
-# Collectives of the partitioned path.  RCCL ("nccl") moves device buffers directly over xGMI; any other backend (gloo in the CPU
-# tests, or gloo with several ranks sharing one GPU in the single-GPU hardware tests) is served by staging through host memory —
-# test transport only, the driver's multi-GPU runs use RCCL.
+# Transport.  RCCL ("nccl") moves device buffers directly over xGMI; any other backend (gloo in the CPU tests, or gloo with several
+# ranks sharing one GPU in the single-GPU hardware tests) is served by staging through host memory — test transport only, the
+# driver's multi-GPU runs use RCCL.
 # =====================================================================================================
 class ThreadWorld:
     """R ranks as R THREADS of one process on ONE GPU (``bench.py --emulate-ranks``, tests): the transport of a :class:`Comm` whose collectives
@@ -291,10 +268,12 @@ class Comm:
         self.tw = thread_world
         if thread_world is not None:          # R ranks as threads of this process (ThreadWorld): device-to-device collectives, timed turns
             self.rank, self.world, self.backend, self.native = int(rank), thread_world.world, "threads", False
-        else:
-            self.rank, self.world = _world(group)
-            self.backend = dist.get_backend(group) if (self.world > 1 or (dist.is_available() and dist.is_initialized())) else None
+        elif dist.is_available() and dist.is_initialized():
+            self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+            self.backend = dist.get_backend(group)
             self.native = self.backend == "nccl"
+        else:
+            self.rank, self.world, self.backend, self.native = 0, 1, None, False
         self._holding = False
         self.sent_bytes = {"exchange": 0, "all_gather": 0, "reduce_scatter": 0, "all_reduce": 0}
         self.events = []               # (kind, bytes to / from the busiest peer, issued asynchronously)
@@ -655,11 +634,8 @@ class Comm:
 
 
 def node_ranges(num_nodes: int, world_size: int) -> list[tuple[int, int]]:
-    return [((num_nodes * r) // world_size, (num_nodes * (r + 1)) // world_size) for r in range(world_size)]
-
-
-def _even_cuts(num_nodes: int, world: int) -> list[int]:
-    return [(num_nodes * r) // world for r in range(world + 1)]
+    cuts = _even_cuts(num_nodes, world_size)
+    return list(zip(cuts[:-1], cuts[1:]))
 
 
 def _ops_default(ops):
@@ -896,12 +872,14 @@ def _shard_rows(source, gs, comm: "Comm | None" = None) -> torch.Tensor:
 
 
 def _window_ends(time: torch.Tensor, his: torch.Tensor, delta) -> torch.Tensor:
-    """:func:`halo_end` for a vector of range ends ``his`` (device tensor), without a host read-back."""
+    """First event id after each range end ``his`` (device int64 tensor) that no source event < ``his`` can reach (see :func:`halo_end`),
+    without a host read-back."""
     m = int(time.numel())
     idx = (his - 1).clamp(min=0, max=max(m - 1, 0))
     delta_t = delta.to(time.device) if isinstance(delta, torch.Tensor) else torch.as_tensor(delta, device=time.device)
-    thr = time[idx] + delta_t
+    thr = time[idx] + delta_t                                     # promoted like the reference's comparison
     if thr.dtype != time.dtype and not time.dtype.is_floating_point:
+        # a float threshold over integer times: float(t) <= thr admits no integer above ceil(thr) + one rounding step of the float type
         t64 = thr.double()
         step = t64.abs() * (2.0 ** -23 if thr.dtype == torch.float32 else 2.0 ** -52) + 1.0
         bound = torch.ceil(t64 + step).clamp(max=float(2 ** 62)).to(torch.int64)
@@ -910,6 +888,15 @@ def _window_ends(time: torch.Tensor, his: torch.Tensor, delta) -> torch.Tensor:
     ends = torch.searchsorted(time, bound.contiguous(), right=True)
     ends = torch.maximum(ends, his)
     return torch.where(his <= 0, torch.zeros_like(his), torch.where(his >= m, torch.full_like(his, m), ends))
+
+
+def _window_share_q(time: torch.Tensor, delta, m: int, dev) -> torch.Tensor:
+    """Device int64 scalar: the share of the stream's time span that one ``delta`` window covers, in 1/1024 (0 for an empty stream)."""
+    if m == 0:
+        return torch.zeros((), dtype=torch.int64, device=dev)
+    span = (time[-1] - time[0]).to(torch.float64).clamp(min=1e-300)
+    delta_t = (delta.to(dev) if isinstance(delta, torch.Tensor) else torch.as_tensor(delta, device=dev)).to(torch.float64)
+    return torch.floor((delta_t / span).clamp(min=0.0, max=1.0) * 1024.0).to(torch.int64)
 
 
 def _balanced_cuts(weights: torch.Tensor, world: int) -> torch.Tensor:
@@ -940,13 +927,7 @@ def partition_plan(ei: torch.Tensor, time: torch.Tensor, n: int, delta, world: i
     dev = ei.device
     m = int(ei.size(1))
     outdeg, indeg = ops.degree(ei[0], n).to(torch.int64), ops.degree(ei[1], n).to(torch.int64)
-    if m > 0:
-        span = (time[-1] - time[0]).to(torch.float64).clamp(min=1e-300)
-        delta_t = (delta.to(dev) if isinstance(delta, torch.Tensor) else torch.as_tensor(delta, device=dev)).to(torch.float64)
-        frac_q = torch.floor((delta_t / span).clamp(min=0.0, max=1.0) * 1024.0).to(torch.int64)      # window share of the stream, in 1/1024
-    else:
-        frac_q = torch.zeros((), dtype=torch.int64, device=dev)
-    node_w = outdeg * (ROW_COST * 1024 + indeg * frac_q) + 1                                          # (+1: empty nodes still get spread)
+    node_w = outdeg * (ROW_COST * 1024 + indeg * _window_share_q(time, delta, m, dev)) + 1            # (+1: empty nodes still get spread)
     fo_cuts_t = _balanced_cuts(node_w, world)
     ev_w = outdeg.index_select(0, ei[1]) + 1 if m else torch.zeros(0, dtype=torch.int64, device=dev)
     ev_cuts_t = _balanced_cuts(ev_w, world)
@@ -1075,6 +1056,28 @@ def _takes_count(fn) -> bool:
     return bool(names) and names[0] in ("num_ho_nodes", "n_ho", "num_nodes")
 
 
+def _per_rank_cached(g, attr: str, comm: Comm, delta, weight: str, build):
+    """``build(edge_index, weights or None)`` of this rank's share of the stream ``g``, cached on ``g`` under ``attr`` per ``(world, rank)``
+    (emulated ranks share the graph object) for as long as ``delta`` and the stream's tensors (identity + in-place version) stay the same."""
+    data = g.data
+    w_all = data[weight] if weight in data else None
+    tensors = (data.edge_index, data.time, w_all)
+    key = (comm.world, comm.rank)
+    cache = getattr(g, attr, None)
+    hit = cache.get(key) if isinstance(cache, dict) else None
+    if hit is not None and hit[0] == repr(delta) and _stamp_matches(hit[1], tensors):
+        return hit[2]
+    shard = build(_dispatch.plain(data.edge_index), w_all)
+    try:
+        if not isinstance(cache, dict):
+            cache = {}
+            object.__setattr__(g, attr, cache)
+        cache[key] = (repr(delta), _stamp(tensors), shard)
+    except Exception:          # exotic containers: no caching, still correct
+        pass
+    return shard
+
+
 class StreamShard:
     """One rank's share of a time-sorted event stream under :func:`partition_plan` — what a multi-GPU deployment holds after it has
     DISTRIBUTED the stream (done once per stream, like the time sort of ``TemporalGraph.__init__``; every step then starts from resident,
@@ -1082,7 +1085,7 @@ class StreamShard:
     events of its lift slice sit in the all-gathered event -> order-2 node maps."""
 
     __slots__ = ("plan", "world", "rank", "n", "m", "ei_l1", "w_l1", "ei_lift", "time_lift", "w_lift", "n_own_lift", "slot", "slot_owner",
-                 "cap_n", "cap_m", "stamp", "delta")
+                 "cap_n", "cap_m", "delta")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -1094,51 +1097,38 @@ def distribute_stream(g, delta, comm: Comm, ops=None, weight: str = "edge_weight
     world stay the same; :func:`build_dbgnn_shard` calls it on first use."""
     ops = _ops_default(ops)
     data = g.data
-    ei = _dispatch.plain(data.edge_index)
-    w_all = data[weight] if weight in data else None
-    stamp = (comm.world, comm.rank, repr(delta), tuple((t_, t_._version) for t_ in (data.edge_index, data.time, w_all) if t_ is not None))
-    cache = getattr(g, "_pp_stream_shards", None)           # {(world, rank): shard} — emulated ranks share the graph object
-    cached = cache.get((comm.world, comm.rank)) if isinstance(cache, dict) else None
-    if cached is not None and len(cached.stamp) == len(stamp) and cached.stamp[:3] == stamp[:3] and len(cached.stamp[3]) == len(stamp[3]) and \
-            all(a is b and va == vb for (a, va), (b, vb) in zip(cached.stamp[3], stamp[3])):
-        return cached
-    rank, world = comm.rank, comm.world
-    dev = ei.device
-    time = data.time.contiguous()
-    n, m = int(data.num_nodes), int(ei.size(1))
-    plan = partition_plan(ei, time, n, delta, world, ops)
-    owner_ptr, order = plan["owner_ptr"], plan["order"].long()
-    lo_e, hi_e = plan["ev_cuts"][rank], plan["ev_cuts"][rank + 1]
-    end_e = max(plan["ev_ends"][rank], hi_e) if hi_e > lo_e else lo_e
-    mine = order[owner_ptr[rank]: owner_ptr[rank + 1]]
-    cap_n = max(max(plan["fo_cuts"][r + 1] - plan["fo_cuts"][r] for r in range(world)), 1)
-    cap_m = max(max(owner_ptr[r + 1] - owner_ptr[r] for r in range(world)), 1)
-    # where the events of my lift slice sit in the [world, cap_n + cap_m] buffer of all-gathered (block sizes | event -> local order-2 node) rows
-    pos_of_event = torch.empty(m, dtype=torch.int64, device=dev)
-    pos_of_event[order] = torch.arange(m, dtype=torch.int64, device=dev)
-    k = pos_of_event[lo_e:end_e]
-    ptr_t = torch.tensor(owner_ptr, dtype=torch.int64, device=dev)
-    q = torch.searchsorted(ptr_t[1:-1].contiguous(), k.contiguous(), right=True) if world > 1 else torch.zeros_like(k)
-    shard = StreamShard(plan=plan, world=world, rank=rank, n=n, m=m, ei_l1=ei.index_select(1, mine).contiguous(),
-                        w_l1=None if w_all is None else w_all.index_select(0, mine).contiguous(), ei_lift=ei[:, lo_e:end_e].contiguous(),
-                        time_lift=time[lo_e:end_e].contiguous(), w_lift=None if w_all is None else w_all[lo_e:end_e].contiguous(),
-                        n_own_lift=hi_e - lo_e, slot=(q * (cap_n + cap_m) + cap_n + (k - ptr_t[q])).contiguous(), slot_owner=q.contiguous(), cap_n=cap_n, cap_m=cap_m,
-                        stamp=stamp, delta=delta)
-    try:
-        if not isinstance(cache, dict):
-            cache = {}
-            object.__setattr__(g, "_pp_stream_shards", cache)
-        cache[(comm.world, comm.rank)] = shard
-    except Exception:          # exotic containers: no caching, still correct
-        pass
-    return shard
+
+    def build(ei, w_all):
+        rank, world = comm.rank, comm.world
+        dev = ei.device
+        time = data.time.contiguous()
+        n, m = int(data.num_nodes), int(ei.size(1))
+        plan = partition_plan(ei, time, n, delta, world, ops)
+        owner_ptr, order = plan["owner_ptr"], plan["order"].long()
+        lo_e, hi_e = plan["ev_cuts"][rank], plan["ev_cuts"][rank + 1]
+        end_e = max(plan["ev_ends"][rank], hi_e) if hi_e > lo_e else lo_e
+        mine = order[owner_ptr[rank]: owner_ptr[rank + 1]]
+        cap_n = max(max(plan["fo_cuts"][r + 1] - plan["fo_cuts"][r] for r in range(world)), 1)
+        cap_m = max(max(owner_ptr[r + 1] - owner_ptr[r] for r in range(world)), 1)
+        # where the events of my lift slice sit in the [world, cap_n + cap_m] buffer of all-gathered (block sizes | event -> local order-2 node) rows
+        pos_of_event = torch.empty(m, dtype=torch.int64, device=dev)
+        pos_of_event[order] = torch.arange(m, dtype=torch.int64, device=dev)
+        k = pos_of_event[lo_e:end_e]
+        ptr_t = torch.tensor(owner_ptr, dtype=torch.int64, device=dev)
+        q = torch.searchsorted(ptr_t[1:-1].contiguous(), k.contiguous(), right=True) if world > 1 else torch.zeros_like(k)
+        return StreamShard(plan=plan, world=world, rank=rank, n=n, m=m, ei_l1=ei.index_select(1, mine).contiguous(),
+                           w_l1=None if w_all is None else w_all.index_select(0, mine).contiguous(), ei_lift=ei[:, lo_e:end_e].contiguous(),
+                           time_lift=time[lo_e:end_e].contiguous(), w_lift=None if w_all is None else w_all[lo_e:end_e].contiguous(),
+                           n_own_lift=hi_e - lo_e, slot=(q * (cap_n + cap_m) + cap_n + (k - ptr_t[q])).contiguous(), slot_owner=q.contiguous(),
+                           cap_n=cap_n, cap_m=cap_m, delta=delta)
+    return _per_rank_cached(g, "_pp_stream_shards", comm, delta, weight, build)
 
 
 class NodeShard:
     """One rank's share of a time-sorted stream under a NODE-RANGE partition (round 4): the events that start or end in its node range, in
     stream order — what the node-by-node order-2 builder wants (pp_debruijn2_part_*).  Built once per stream (cached on the graph)."""
 
-    __slots__ = ("world", "rank", "n", "m", "fo_cuts", "cuts_t", "ei", "time", "w", "stamp")
+    __slots__ = ("world", "rank", "n", "m", "fo_cuts", "cuts_t", "ei", "time", "w")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -1150,41 +1140,22 @@ def distribute_stream_by_node(g, delta, comm: Comm, ops=None, weight: str = "edg
     every rank, no collective) + this rank's events: those with the tail OR the head node in its range.  Cached on ``g``."""
     ops = _ops_default(ops)
     data = g.data
-    ei = _dispatch.plain(data.edge_index)
-    w_all = data[weight] if weight in data else None
-    stamp = (comm.world, comm.rank, repr(delta), tuple((t_, t_._version) for t_ in (data.edge_index, data.time, w_all) if t_ is not None))
-    cache = getattr(g, "_pp_node_shards", None)
-    cached = cache.get((comm.world, comm.rank)) if isinstance(cache, dict) else None
-    if cached is not None and len(cached.stamp) == len(stamp) and cached.stamp[:3] == stamp[:3] and len(cached.stamp[3]) == len(stamp[3]) and \
-            all(a is b and va == vb for (a, va), (b, vb) in zip(cached.stamp[3], stamp[3])):
-        return cached
-    rank, world = comm.rank, comm.world
-    dev = ei.device
-    time = data.time.contiguous()
-    n, m = int(data.num_nodes), int(ei.size(1))
-    outdeg, indeg = ops.degree(ei[0], n).to(torch.int64), ops.degree(ei[1], n).to(torch.int64)
-    if m > 0:
-        span = (time[-1] - time[0]).to(torch.float64).clamp(min=1e-300)
-        delta_t = (delta.to(dev) if isinstance(delta, torch.Tensor) else torch.as_tensor(delta, device=dev)).to(torch.float64)
-        frac_q = torch.floor((delta_t / span).clamp(min=0.0, max=1.0) * 1024.0).to(torch.int64)
-    else:
-        frac_q = torch.zeros((), dtype=torch.int64, device=dev)
-    # a node b costs its events on both sides (sorted, gathered) + its rows (b, .) + its expected in-edges in(b) * out(b) * delta / span
-    node_w = (outdeg + indeg) * 1024 + outdeg * (ROW_COST * 1024 + indeg * frac_q) + 1
-    cuts_t = _balanced_cuts(node_w, world)
-    fo_cuts = cuts_t.tolist()
-    lo, hi = fo_cuts[rank], fo_cuts[rank + 1]
-    mine = torch.nonzero(((ei[0] >= lo) & (ei[0] < hi)) | ((ei[1] >= lo) & (ei[1] < hi))).flatten()
-    shard = NodeShard(world=world, rank=rank, n=n, m=m, fo_cuts=fo_cuts, cuts_t=cuts_t.contiguous(), ei=ei.index_select(1, mine).contiguous(),
-                      time=time.index_select(0, mine).contiguous(), w=None if w_all is None else w_all.index_select(0, mine).contiguous(), stamp=stamp)
-    try:
-        if not isinstance(cache, dict):
-            cache = {}
-            object.__setattr__(g, "_pp_node_shards", cache)
-        cache[(comm.world, comm.rank)] = shard
-    except Exception:
-        pass
-    return shard
+
+    def build(ei, w_all):
+        rank, world = comm.rank, comm.world
+        dev = ei.device
+        time = data.time.contiguous()
+        n, m = int(data.num_nodes), int(ei.size(1))
+        outdeg, indeg = ops.degree(ei[0], n).to(torch.int64), ops.degree(ei[1], n).to(torch.int64)
+        # a node b costs its events on both sides (sorted, gathered) + its rows (b, .) + its expected in-edges in(b) * out(b) * delta / span
+        node_w = (outdeg + indeg) * 1024 + outdeg * (ROW_COST * 1024 + indeg * _window_share_q(time, delta, m, dev)) + 1
+        cuts_t = _balanced_cuts(node_w, world)
+        fo_cuts = cuts_t.tolist()
+        lo, hi = fo_cuts[rank], fo_cuts[rank + 1]
+        mine = torch.nonzero(((ei[0] >= lo) & (ei[0] < hi)) | ((ei[1] >= lo) & (ei[1] < hi))).flatten()
+        return NodeShard(world=world, rank=rank, n=n, m=m, fo_cuts=fo_cuts, cuts_t=cuts_t.contiguous(), ei=ei.index_select(1, mine).contiguous(),
+                         time=time.index_select(0, mine).contiguous(), w=None if w_all is None else w_all.index_select(0, mine).contiguous())
+    return _per_rank_cached(g, "_pp_node_shards", comm, delta, weight, build)
 
 
 def _own_rows_buffer(source, lo: int, hi: int, row_of: torch.Tensor, n_halo: int, device) -> torch.Tensor:
@@ -1404,89 +1375,55 @@ from .nn.sharded import ShardedDBGNN  # noqa: E402,F401  (historic import locati
 # (+ weight) to its owner, the owner coalesces its range with the single-GPU kernels, and an all-gather of the per-rank counts
 # turns local ranks into global ids.  Concatenating the ranks' outputs in rank order IS the single-process result.
 # =====================================================================================================
-def _exchange(buckets: list[torch.Tensor], group=None) -> torch.Tensor:
-    """Send ``buckets[r]`` to rank r, return the concatenation of what the other ranks sent here (rank order).
-    RCCL: one all_to_all of the sizes + one of the payload; gloo (tests) has no all_to_all: all-gather and pick."""
-    rank, world = _world(group)
-    if not (dist.is_available() and dist.is_initialized()):
-        return buckets[0]
-    if dist.get_backend(group) == "nccl":
-        send_sizes = torch.tensor([b.size(0) for b in buckets], dtype=torch.int64, device=buckets[0].device)
-        recv_sizes = torch.empty_like(send_sizes)
-        dist.all_to_all_single(recv_sizes, send_sizes, group=group)
-        recv = list(torch.empty((int(recv_sizes.sum()),) + tuple(buckets[0].shape[1:]), dtype=buckets[0].dtype,
-                                device=buckets[0].device).split(recv_sizes.tolist()))
-        dist.all_to_all(recv, [b.contiguous() for b in buckets], group=group)
-        return torch.cat(recv, dim=0)
-    gathered = [None] * world
-    dist.all_gather_object(gathered, [b.cpu() for b in buckets], group=group)
-    return torch.cat([gathered[src][rank] for src in range(world)], dim=0).to(buckets[0].device)
-
-
-def _owner_cuts(num_keys_space: int, world: int) -> torch.Tensor:
-    """Equal-width key ranges over ``[0, num_keys_space)``: ``cuts[r] .. cuts[r+1]`` is owned by rank r."""
-    return torch.tensor([(num_keys_space * r) // world for r in range(world + 1)], dtype=torch.int64)
-
-
-def coalesce_sharded(rows: torch.Tensor, cols: torch.Tensor, weight: torch.Tensor, num_nodes: int, group=None):
+def coalesce_sharded(rows: torch.Tensor, cols: torch.Tensor, weight: torch.Tensor, num_nodes: int, group=None, *,
+                     comm: "Comm | None" = None, ops=None):
     """Global ``coalesce`` of edges scattered over the ranks.  Rank r ends up with the distinct edges whose ROW lies in
     ``[cuts[r], cuts[r+1])`` (sorted by (row, col), weights summed); returns ``(edge_index [2, A_r], weight [A_r], cuts)``."""
-    rank, world = _world(group)
-    cuts = _owner_cuts(num_nodes, world).to(rows.device)
+    comm = Comm(group) if comm is None else comm
+    ops = _dispatch if ops is None else ops
+    world = comm.world
+    cuts = torch.tensor(_even_cuts(num_nodes, world), dtype=torch.int64, device=rows.device)      # equal-width key ranges
     owner = torch.searchsorted(cuts[1:].contiguous(), rows, right=True).clamp_(max=world - 1)
     # ids and weights travel separately: the weights keep their dtype (integer weights stay exact beyond 2^24, ADVICE r1)
     order = torch.sort(owner, stable=True).indices
-    counts = torch.bincount(owner, minlength=world).tolist()
-    ids = torch.stack((rows, cols), dim=1).index_select(0, order)
-    wsorted = weight.index_select(0, order)
-    mine = _exchange(list(ids.split(counts)), group)
-    w = _exchange(list(wsorted.split(counts)), group)
-    ei = mine.t().contiguous()
-    merged_index, merged_weight = _dispatch.coalesce(ei, w.contiguous(), num_nodes, "sum")
+    send = torch.bincount(owner, minlength=world).tolist()
+    recv = comm.exchange_counts(send, rows.device)
+    ids = comm.exchange_rows(torch.stack((rows, cols), dim=1).index_select(0, order), send, recv)
+    w = comm.exchange_rows(weight.index_select(0, order), send, recv)
+    merged_index, merged_weight = ops.coalesce(ids.t().contiguous(), w.contiguous(), num_nodes, "sum")
     return merged_index, merged_weight, cuts.cpu()
 
 
-def unique_pairs_sharded(src: torch.Tensor, dst: torch.Tensor, num_nodes: int, group=None):
+def unique_pairs_sharded(src: torch.Tensor, dst: torch.Tensor, num_nodes: int, group=None, *, comm: "Comm | None" = None, ops=None):
     """Global lexicographic numbering of the distinct (src, dst) pairs of events scattered over the ranks (= the order-2
     De Bruijn nodes).  Returns ``(all_pairs [U, 2] on every rank, ids)`` with ``ids[e]`` the global id of local event e."""
-    rank, world = _world(group)
+    comm = Comm(group) if comm is None else comm
     ones = torch.ones(src.numel(), dtype=torch.float32, device=src.device)
-    local_pairs, _, _ = coalesce_sharded(src, dst, ones, num_nodes, group)          # my key range, sorted, distinct
-    counts = torch.tensor([local_pairs.size(1)], dtype=torch.int64, device=src.device)
-    if world > 1:
-        sizes = [torch.zeros_like(counts) for _ in range(world)]
-        dist.all_gather(sizes, counts, group=group)
-        cap = max(int(s.item()) for s in sizes)
-        padded = torch.zeros((2, cap), dtype=torch.int64, device=src.device)
-        padded[:, : local_pairs.size(1)] = local_pairs
-        parts = [torch.empty_like(padded) for _ in range(world)]
-        dist.all_gather(parts, padded, group=group)
-        all_pairs = torch.cat([p[:, : int(s.item())] for p, s in zip(parts, sizes)], dim=1)
-    else:
-        all_pairs = local_pairs
+    local_pairs, _, _ = coalesce_sharded(src, dst, ones, num_nodes, comm=comm, ops=ops)        # my key range, sorted, distinct
+    all_pairs = _gather_columns(local_pairs, comm)
     keys = all_pairs[0] * num_nodes + all_pairs[1]                                   # ascending: ranks own ascending row ranges
     ids = torch.searchsorted(keys.contiguous(), (src * num_nodes + dst).contiguous())
     return all_pairs.t().contiguous(), ids
 
 
-def second_order_layer_sharded(g, delta=1, group=None, edge_weight: torch.Tensor | None = None) -> dict:
+def second_order_layer_sharded(g, delta=1, group=None, edge_weight: torch.Tensor | None = None, *, comm: "Comm | None" = None, ops=None) -> dict:
     """Order-2 De Bruijn layer of a temporal graph replicated on every rank, computed cooperatively: edge-range lift (no
     exchange), global pair numbering (one exchange), global coalesce of the lifted pairs (one exchange).
     Rank r returns its slice of the layer: the aggregated edges whose source node id lies in its row range."""
-    rank, world = _world(group)
+    comm = Comm(group) if comm is None else comm
     data = g.data
     ei = _dispatch.plain(data.edge_index)
     n = int(data.num_nodes)
     w = edge_weight if edge_weight is not None else torch.ones(ei.size(1), device=ei.device)
-    local, _, total = lift_order_temporal_sharded(g, delta, group)                 # (i, j) with global event ids
-    lo, hi = event_ranges(ei.size(1), world)[rank]
-    pairs, own_ids = unique_pairs_sharded(ei[0, lo:hi], ei[1, lo:hi], n, group)     # every rank contributes its own events
+    local, _, total = lift_order_temporal_sharded(g, delta, comm=comm, ops=ops)                 # (i, j) with global event ids
+    lo, hi = event_ranges(ei.size(1), comm.world)[comm.rank]
+    pairs, own_ids = unique_pairs_sharded(ei[0, lo:hi], ei[1, lo:hi], n, comm=comm, ops=ops)     # every rank contributes its own events
     num_ho = pairs.size(0)
     # node id of EVERY event the local pairs refer to (own events and halo): look the pair up in the global list
     pair_keys = (pairs[:, 0] * n + pairs[:, 1]).contiguous()
     i, j = local[0], local[1]
     u = torch.searchsorted(pair_keys, (ei[0][i] * n + ei[1][i]).contiguous())
     v = torch.searchsorted(pair_keys, (ei[0][j] * n + ei[1][j]).contiguous())
-    edges, weights, cuts = coalesce_sharded(u, v, w[i], num_ho, group)
+    edges, weights, cuts = coalesce_sharded(u, v, w[i], num_ho, comm=comm, ops=ops)
     return {"edge_index": edges, "edge_weight": weights, "node_sequence": pairs, "num_nodes": num_ho, "row_cuts": cuts,
             "instance_pairs_total": total, "own_event_ids": own_ids}

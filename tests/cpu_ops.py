@@ -134,6 +134,13 @@ class CpuOps:
         return out + id_offset
 
     @staticmethod
+    def linegraph_lift(edge_index, num_nodes, edge_range=None):
+        out = ol.line_graph_lift(edge_index, num_nodes)
+        if edge_range is not None:
+            out = out[:, (out[0] >= edge_range[0]) & (out[0] < edge_range[1])]
+        return out
+
+    @staticmethod
     def coalesce_and_lift(coalesce_args, lift_args):
         return CpuOps.coalesce(*coalesce_args), CpuOps.temporal_lift(*lift_args)
 

@@ -38,17 +38,47 @@ def test_halo_end_matches_definition():
     assert halo_end(t, 1, 100) == 9
 
 
-def _oracle_local_lift(edge_index, time, num_nodes, delta, n_own=None, id_offset=0):
-    out = ol.temporal_lift_sorted(edge_index, time, delta, num_nodes)
-    if n_own is not None:
-        out = out[:, out[0] < n_own]
-    return out + id_offset
-
-
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         return s.getsockname()[1]
+
+
+def _lift_checks(rank, world, seed, comm=None):
+    """Sharded temporal and line-graph lifts, gather_lifted and the gradient all-reduce against the oracle, the local lifts by CpuOps.
+    ``comm=None``: the primitives' default ``Comm`` of the initialised process group."""
+    import pathpyg_amd as pp
+    from pathpyg_amd import distributed as pd
+    from tests.cpu_ops import CpuOps
+    ops = CpuOps()
+    rng = np.random.default_rng(seed)
+    m, n = 3000, 25
+    ei = torch.from_numpy(rng.integers(0, n, (2, m)))
+    t = torch.from_numpy(np.sort(rng.integers(0, 400, m)))
+    g = type("G", (), {})()
+    g.data = pp.Data(edge_index=ei, time=t, num_nodes=n)
+    want = ol.temporal_lift_sorted(ei, t, 9, n)
+    for weights in (None, torch.from_numpy(rng.random(m))):
+        local, offset, total = pd.lift_order_temporal_sharded(g, delta=9, weights=weights, comm=comm, ops=ops)
+        assert total == want.size(1)
+        assert torch.equal(local, want[:, offset: offset + local.size(1)])      # my block of the global result
+        full = pd.gather_lifted(local, comm=comm)
+        assert torch.equal(full, want)
+    # edge-range sharded LINE-GRAPH lift of the (source-sorted) event graph: blocks concatenate to the single-process result
+    want3 = ol.line_graph_lift(want, m)
+    for weights in (None, torch.from_numpy(rng.random(want.size(1)))):
+        local3, ranges3, total3 = pd.lift_order_edge_index_sharded(want, m, weights=weights, comm=comm, ops=ops)
+        assert total3 == want3.size(1)
+        lo3, hi3 = ranges3[rank]
+        assert torch.equal(local3, want3[:, (want3[0] >= lo3) & (want3[0] < hi3)])
+        assert torch.equal(pd.gather_lifted(local3, comm=comm), want3)
+    # gradient all-reduce: mean over ranks, one flattened collective
+    net = pp.nn.DBGNN(num_classes=2, num_features=(3, 3), hidden_dims=[4, 4, 2])
+    for i, p in enumerate(net.parameters()):
+        p.grad = torch.full_like(p, float(rank + 1) * (i + 1))
+    pd.all_reduce_gradients(net, comm=comm)
+    for i, p in enumerate(net.parameters()):
+        assert torch.allclose(p.grad, torch.full_like(p, (i + 1) * (1 + world) / 2))
 
 
 def _worker(rank, world, port, seed, results):
@@ -56,41 +86,7 @@ def _worker(rank, world, port, seed, results):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        import pathpyg_amd as pp
-        from pathpyg_amd import _dispatch, distributed as pd
-        _dispatch.temporal_lift = _oracle_local_lift          # test-only substitution of the GPU kernel
-        rng = np.random.default_rng(seed)
-        m, n = 3000, 25
-        ei = torch.from_numpy(rng.integers(0, n, (2, m)))
-        t = torch.from_numpy(np.sort(rng.integers(0, 400, m)))
-        g = type("G", (), {})()
-        g.data = pp.Data(edge_index=ei, time=t, num_nodes=n)
-        want = ol.temporal_lift_sorted(ei, t, 9, n)
-        for weights in (None, torch.from_numpy(rng.random(m))):
-            local, offset, total = pd.lift_order_temporal_sharded(g, delta=9, weights=weights)
-            assert total == want.size(1)
-            assert torch.equal(local, want[:, offset: offset + local.size(1)])      # my block of the global result
-            full = pd.gather_lifted(local)
-            assert torch.equal(full, want)
-        # edge-range sharded LINE-GRAPH lift of the (source-sorted) event graph: blocks concatenate to the single-process result
-        def oracle_range_lift(edge_index, num_nodes, edge_range=None):
-            full_lift = ol.line_graph_lift(edge_index, num_nodes)
-            lo_, hi_ = edge_range
-            return full_lift[:, (full_lift[0] >= lo_) & (full_lift[0] < hi_)]
-        _dispatch.linegraph_lift = oracle_range_lift
-        want3 = ol.line_graph_lift(want, m)
-        local3, ranges3, total3 = pd.lift_order_edge_index_sharded(want, m)
-        assert total3 == want3.size(1)
-        lo3, hi3 = ranges3[rank]
-        assert torch.equal(local3, want3[:, (want3[0] >= lo3) & (want3[0] < hi3)])
-        assert torch.equal(pd.gather_lifted(local3), want3)
-        # gradient all-reduce: mean over ranks, one flattened collective
-        net = pp.nn.DBGNN(num_classes=2, num_features=(3, 3), hidden_dims=[4, 4, 2])
-        for i, p in enumerate(net.parameters()):
-            p.grad = torch.full_like(p, float(rank + 1) * (i + 1))
-        pd.all_reduce_gradients(net)
-        for i, p in enumerate(net.parameters()):
-            assert torch.allclose(p.grad, torch.full_like(p, (i + 1) * (1 + world) / 2))
+        _lift_checks(rank, world, seed)
         results[rank] = "ok"
     finally:
         dist.destroy_process_group()
@@ -603,10 +599,32 @@ def test_node_range_partition_world8_threads_match_oracle():
 
 # ------------------------------------------------------------------------------------------------------------------
 # Distributed aggregation: range-partitioned keys, one exchange per layer (gloo; the local coalesce is the oracle's).
-def _oracle_coalesce(edge_index, weight, num_nodes, reduce="sum", remap=None, want_inverse=False, col_block=None):
-    from oracle import aggregate as oa
-    assert remap is None and not want_inverse
-    return oa.coalesce(edge_index, weight, num_nodes, reduce)
+def _layer2_checks(rank, world, comm=None):
+    """The rank's slice of second_order_layer_sharded against the oracle's layer 2, the local lift and coalesce by CpuOps."""
+    import pathpyg_amd as pp
+    from pathpyg_amd import distributed as pd
+    from oracle import model as om
+    from tests.cpu_ops import CpuOps
+    rng = np.random.default_rng(17)
+    m, n, delta = 4000, 30, 11
+    ei = torch.from_numpy(rng.integers(0, n, (2, m)))
+    t = torch.from_numpy(np.sort(rng.integers(0, 500, m)))
+    w = torch.from_numpy(rng.integers(1, 4, m).astype(np.float32))
+    g = type("G", (), {})()
+    g.data = pp.Data(edge_index=ei, time=t, num_nodes=n)
+    want = om.layers_from_temporal(ei, t, n, delta=delta, max_order=2, edge_weight=w)[2]
+    part = pd.second_order_layer_sharded(g, delta=delta, edge_weight=w, comm=comm, ops=CpuOps())
+    assert torch.equal(part["node_sequence"], want["node_sequence"]) and part["num_nodes"] == want["num_nodes"]
+    lo, hi = pd.event_ranges(m, world)[rank]
+    assert torch.equal(part["own_event_ids"], want["inverse_idx"][lo:hi])          # global node ids of my events
+    # my slice = the reference layer's edges whose row falls into my row range; slices concatenate to the whole layer
+    cuts = part["row_cuts"]
+    rows = want["edge_index"][0]
+    mine = (rows >= cuts[rank]) & (rows < cuts[rank + 1])
+    assert torch.equal(part["edge_index"], want["edge_index"][:, mine])
+    assert torch.equal(part["edge_weight"], want["edge_weight"][mine])
+    sizes = (pd.Comm() if comm is None else comm).all_gather_ints([part["edge_index"].size(1)], ei.device)
+    assert sum(r[0] for r in sizes) == want["edge_index"].size(1)
 
 
 def _agg_worker(rank, world, port, results):
@@ -614,32 +632,7 @@ def _agg_worker(rank, world, port, results):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        import pathpyg_amd as pp
-        from pathpyg_amd import _dispatch, distributed as pd
-        from oracle import model as om
-        _dispatch.temporal_lift = _oracle_local_lift
-        _dispatch.coalesce = _oracle_coalesce
-        rng = np.random.default_rng(17)
-        m, n, delta = 4000, 30, 11
-        ei = torch.from_numpy(rng.integers(0, n, (2, m)))
-        t = torch.from_numpy(np.sort(rng.integers(0, 500, m)))
-        w = torch.from_numpy(rng.integers(1, 4, m).astype(np.float32))
-        g = type("G", (), {})()
-        g.data = pp.Data(edge_index=ei, time=t, num_nodes=n)
-        want = om.layers_from_temporal(ei, t, n, delta=delta, max_order=2, edge_weight=w)[2]
-        part = pd.second_order_layer_sharded(g, delta=delta, edge_weight=w)
-        assert torch.equal(part["node_sequence"], want["node_sequence"]) and part["num_nodes"] == want["num_nodes"]
-        lo, hi = pd.event_ranges(m, world)[rank]
-        assert torch.equal(part["own_event_ids"], want["inverse_idx"][lo:hi])          # global node ids of my events
-        # my slice = the reference layer's edges whose row falls into my row range; slices concatenate to the whole layer
-        cuts = part["row_cuts"]
-        rows = want["edge_index"][0]
-        mine = (rows >= cuts[rank]) & (rows < cuts[rank + 1])
-        assert torch.equal(part["edge_index"], want["edge_index"][:, mine])
-        assert torch.equal(part["edge_weight"], want["edge_weight"][mine])
-        sizes = [None] * world
-        dist.all_gather_object(sizes, int(part["edge_index"].size(1)))
-        assert sum(sizes) == want["edge_index"].size(1)
+        _layer2_checks(rank, world)
         results[rank] = "ok"
     finally:
         dist.destroy_process_group()
@@ -657,3 +650,17 @@ def test_sharded_second_order_layer_matches_oracle(world):
         p.join(240)
         assert p.exitcode == 0
     assert dict(results) == {r: "ok" for r in range(world)}
+
+
+@pytest.mark.parametrize("world", [3, 8])
+def test_stream_primitives_on_thread_world_match_oracle(world):
+    """The same checks as the gloo workers above with the ranks as threads of one process (ThreadWorld): the primitives' collectives go
+    through the ``comm`` they are handed, their device work through ``ops``."""
+    from pathpyg_amd import distributed as pd
+
+    def body(comm):
+        _lift_checks(comm.rank, comm.world, 5, comm)
+        _layer2_checks(comm.rank, comm.world, comm)
+        return "ok"
+
+    assert pd.run_thread_world(world, body) == ["ok"] * world

@@ -199,6 +199,42 @@ def test_partition_path_three_ranks_as_threads_match_oracle():
     assert pd.run_thread_world(3, body, dev) == ["ok"] * 3
 
 
+def test_stream_primitives_eight_ranks_as_threads_match_single_process():
+    """The stream primitives on 8 emulated ranks with the real kernels: the concatenated second_order_layer_sharded slices are the
+    single-process layer 2, and gather_lifted of every rank's sharded lift block is the whole lift."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU visible")
+    import pathpyg_amd as pp
+    from pathpyg_amd import _hip, distributed as pd
+    from oracle import model as om
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(5)
+    m, n, delta = 20_000, 200, 9
+    ei = torch.from_numpy(rng.integers(0, n, (2, m)))
+    t = torch.from_numpy(np.sort(rng.integers(0, 3000, m)))
+    w = torch.from_numpy(rng.integers(1, 4, m).astype(np.float32))
+    g = pp.TemporalGraph(pp.Data(edge_index=ei.to(dev), time=t.to(dev), num_nodes=n))
+    want = om.layers_from_temporal(ei, t, n, delta=delta, max_order=2, edge_weight=w)[2]
+    want_lift = _hip.temporal_lift(ei.to(dev), t.to(dev), n, delta).cpu()
+    want_line = _hip.linegraph_lift(want_lift.to(dev), m).cpu()
+
+    def body(comm):
+        part = pd.second_order_layer_sharded(g, delta=delta, edge_weight=w.to(dev), comm=comm)
+        local, _, total = pd.lift_order_temporal_sharded(g, delta, comm=comm)
+        local3, _, total3 = pd.lift_order_edge_index_sharded(want_lift.to(dev), m, comm=comm)
+        return {k: (v.cpu() if isinstance(v, torch.Tensor) else v) for k, v in part.items()} | {
+            "lifted": pd.gather_lifted(local, comm=comm).cpu(), "total": total, "line": pd.gather_lifted(local3, comm=comm).cpu(), "total3": total3}
+
+    parts = pd.run_thread_world(8, body, dev)
+    for part in parts:
+        assert torch.equal(part["node_sequence"], want["node_sequence"]) and part["num_nodes"] == want["num_nodes"]
+        assert torch.equal(part["lifted"], want_lift) and part["total"] == want_lift.size(1)
+        assert torch.equal(part["line"], want_line) and part["total3"] == want_line.size(1)
+    assert torch.equal(torch.cat([p["edge_index"] for p in parts], dim=1), want["edge_index"])
+    assert torch.equal(torch.cat([p["edge_weight"] for p in parts]), want["edge_weight"])
+    assert torch.equal(torch.cat([p["own_event_ids"] for p in parts]), want["inverse_idx"])
+
+
 def test_emulation_clocks_events_and_drain_agree_on_results_and_log_every_asynchronous_collective():
     """bench.py --emulate-clock: the "events" clock (turns bracketed by stream events, nothing drained at the collectives; the ranks' data hand-offs
     are ordered by the shared stream alone) must give the results of the "drain" clock, positive device and host times per rank, and one
