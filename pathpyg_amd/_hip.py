@@ -11,7 +11,7 @@ import threading
 
 import torch
 
-from ._lib import check, lib
+from ._lib import HipError, check, lib
 
 _DTYPE_CODE = {torch.int32: 0, torch.int64: 1, torch.float32: 2, torch.float64: 3}
 _EDGE_AGGR = {"src": 0, "dst": 1, "max": 2, "mul": 3, "add": 4}
@@ -362,6 +362,8 @@ def coalesce_steps(edge_index: torch.Tensor, weight, num_nodes: int, reduce: str
     col_base, col_bits = (None, 0) if col_block is None else (col_block[0].to(torch.int64).contiguous(), int(col_block[1]))
     if col_base is not None and col_base.numel() != num_nodes:
         raise ValueError("col_base must hold one entry per node")
+    if e >= 0x7fffffff:          # (pp_coalesce_count's refusal, before a workspace of ~40 bytes per edge is allocated for it)
+        raise HipError(f"pp_coalesce_count: more than 2^31 edges ({e})")
     L = lib()
     with torch.cuda.device(dev):
         ws = _workspace(L.pp_coalesce_ws_bytes(e), dev)
@@ -789,7 +791,10 @@ def debruijn2(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delt
     ``want_weights``: also keep the merged order-2 weights themselves (``ho_fwd_weight`` [A2], destination-major order, beside the normalised
     coefficients of the plan) — what ``MultiOrderModel.layers[2].data.edge_weight`` is derived from when it is read.
     Returns a :class:`DeBruijn2`, or ``None`` when the builder does not apply (an empty stream, a weight vector that is not float32, more than
-    2^31 order-2 edges, hub partials beyond 24 GiB; with ``unsorted_ok`` an unsorted stream): the caller then takes the generic path."""
+    2^31 order-2 edges, hub partials beyond 24 GiB; with ``unsorted_ok`` an unsorted stream): the caller then takes the generic path.
+    Merged weights: layer 1 is the reference's left-to-right sum (the float64 sum rounded once from 2^24 on, exact counts for unit weights).
+    Layer 2 through a hub node is summed in (in-event, task) order: equal to the reference's sum for integer-valued weights below 2^24,
+    otherwise within (len - 1) * 2^-24 * sum|w| of the exact sum of an edge's len instances - the one association that differs."""
     ei = _edge_index(edge_index)
     dev = require_device(ei, time, weight)
     stream = _event_stream(ei, time, weight)

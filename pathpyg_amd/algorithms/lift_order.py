@@ -54,6 +54,11 @@ def aggregate_edge_index(
     order), parallel edges are merged and their weights reduced with ``aggr`` ("sum", "mean", "min",
     "max").  The returned graph stores ``edge_index``, ``edge_weight``, ``node_sequence`` (unique rows),
     ``inverse_idx`` (node id of every input row) and ``num_nodes``.
+
+    Differences from the reference: without weights a merged edge weighs float32(its number of copies) - the reference sums ones
+    and stops at 16777216.0.  Weights are summed left to right, bit for bit the reference's float32 sum, with one exception: a run of
+    more than 512 copies whose float32 sum reaches 2^24 gets the float64 sum rounded once (shorter runs keep the reference's sum,
+    which stalls there).  2^31 or more edges raise ``HipError``.
     """
     if edge_weight is None:
         edge_weight = _hip.UNIT          # the reference's torch.ones (:130-131) without the vector: a merged weight is its run length

@@ -86,7 +86,13 @@ class MultiOrderModel:
         ``event_graph`` reuses a precomputed ``lift_order_temporal(g, delta)``.
 
         Same layers as the reference, computed without ever materialising the per-instance node sequences
-        (``[E_k, k+1]`` tensors): see :class:`_LiftChain`."""
+        (``[E_k, k+1]`` tensors): see :class:`_LiftChain`.  Merged weights are the reference's left-to-right fp32 sums while they
+        stay below 2^24.  Beyond, where that sum stalls (ones stop at 16777216.0), a unit-weight edge weighs float32(its count); a
+        weighted sum is the float64 sum rounded once for the LONG runs - more than 512 instances on the generic kernels, a first-order
+        node pair of more than 128 events on the level-by-level builder, a first-order run of a node with more than 64 out-events on
+        the order-2 builder - and the reference's stalled sum for all others, so routes may differ there.  The order-2 builder's layer 2
+        through nodes with more than 64 events per side sums in another association (see ``_hip.debruijn2``).  A stream with 2^31 or
+        more instances at some order raises ``HipError``."""
         if max_order == 2 and event_graph is None and FUSED_BUILDER:
             # LIFT_ONLY_ORDER2 (off by default): a stream with a very large hub (BASELINE configs[2]'s generator: a node with 2 * 10^6 in-events) costs
             # the order-2 builder's hub kernels 10-11 ms where the level-by-level builder makes both layers in 5.3-5.7 ms — but it makes no GCN

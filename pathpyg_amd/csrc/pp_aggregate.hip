@@ -210,20 +210,63 @@ __global__ __launch_bounds__(kBlock) void k_coalesce_fill(const KeyT* __restrict
     out_weight[a] = reduce == PP_REDUCE_MEAN ? mean_of<T>(acc, len) : acc;
 }
 
-// One workgroup per queued run: 256 threads stride over it with 8 gathers in flight each; partial results are folded in a fixed order
-// (wave butterfly, then the waves in wave order) - sums of integer-valued weights stay exact, other float sums differ from the
-// left-to-right order only by rounding.  The queue order is arbitrary, the result of each run is not.
+// One workgroup per queued run.  Float sums and means are folded LEFT TO RIGHT, PyG's order: the workgroup gathers kFold weights at a time
+// into LDS (8 gathers in flight per thread) and thread 0 adds them in order (fold_ltr) - only the adds are serial, so the time grows with
+// the longest run.  An fp32 sum that reaches 2^24, where the reference's left-to-right sum stalls (a sum of ones stops at 2^24), is the
+// float64 sum rounded once instead (summed by all threads during the gathers), as unit weights are written as exact run lengths.  Integer sums and min / max do not depend on the order: 256 threads stride over the run and the
+// partial results are folded in a fixed order (wave butterfly, then the waves in wave order).  The queue order is arbitrary, the result of
+// each run is not.
+template <typename T>
+__device__ __forceinline__ T fold_result(T ltr, double exact) {
+    if constexpr (std::is_same<T, float>::value) return fabsf(ltr) < 16777216.f ? ltr : (float)exact;
+    else return ltr;
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void k_coalesce_long_runs(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ seg_start,
                                                               const T* __restrict__ weight, int reduce, const uint32_t* __restrict__ long_runs,
                                                               T* __restrict__ out_weight) {
+    constexpr int kUnroll = 8;
+    constexpr bool kFloat = std::is_floating_point<T>::value;
+    constexpr int kFold = kFloat ? kUnroll * kBlock : 1;
     __shared__ T s_part[kWavesPerBlock];
+    __shared__ double s_exact[kWavesPerBlock];
+    __shared__ __attribute__((aligned(16))) T s_fold[kFold];
     const uint32_t count = long_runs[0];
+    const bool ordered = kFloat && (reduce == PP_REDUCE_SUM || reduce == PP_REDUCE_MEAN);
     for (uint32_t k = blockIdx.x; k < count; k += gridDim.x) {
         const uint32_t a = long_runs[1 + k];
         const uint32_t b = seg_start[a], e = seg_start[a + 1];
+        if (ordered) {
+            T acc = (T)0;                                           // (the reference adds into zeros: index_add_)
+            double exact = 0.0;                                     // this thread's share of the float64 sum
+            for (uint32_t base = b; base < e; base += kFold) {
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    const uint32_t p = base + u * kBlock + threadIdx.x;
+                    if (p < e) {
+                        const T v = weight[perm[p]];
+                        s_fold[u * kBlock + threadIdx.x] = v;
+                        exact += (double)v;
+                    }
+                }
+                __syncthreads();
+                if (threadIdx.x == 0) fold_ltr<T>(s_fold, e - base < (uint32_t)kFold ? e - base : (uint32_t)kFold, acc);
+                __syncthreads();
+            }
+            exact = wave_sum<double>(exact);
+            if (lane_id() == 0) s_exact[wave_id()] = exact;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+#pragma unroll
+                for (int w = 1; w < kWavesPerBlock; ++w) exact += s_exact[w];
+                acc = fold_result<T>(acc, exact);
+                out_weight[a] = reduce == PP_REDUCE_MEAN ? mean_of<T>(acc, e - b) : acc;
+            }
+            __syncthreads();
+            continue;
+        }
         T part = weight[perm[b + threadIdx.x]];                     // len > kLongRun >= kBlock: every thread starts from its own element
-        constexpr int kUnroll = 8;
         uint32_t p = b + kBlock + threadIdx.x;
         for (; p + (kUnroll - 1) * kBlock < e; p += kUnroll * kBlock) {
             T ww[kUnroll];

@@ -83,6 +83,31 @@ __device__ __forceinline__ T wave_inclusive_sum(T v) {
     return v;
 }
 
+// acc += s[0] + s[1] + ... + s[n-1] LEFT TO RIGHT (PyG's order) on one lane: the LDS reads run 16 values ahead of the adds, which are
+// then the only serial part
+template <typename T>
+__device__ __forceinline__ void fold_ltr(const T* s, uint32_t n, T& acc) {
+    constexpr uint32_t kAhead = 16;
+    uint32_t i = 0;
+    if (n >= kAhead) {
+        T cur[kAhead];
+#pragma unroll
+        for (uint32_t u = 0; u < kAhead; ++u) cur[u] = s[u];
+        for (i = kAhead; i + kAhead <= n; i += kAhead) {
+            T nxt[kAhead];
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u) nxt[u] = s[i + u];
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u) acc += cur[u];
+#pragma unroll
+            for (uint32_t u = 0; u < kAhead; ++u) cur[u] = nxt[u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kAhead; ++u) acc += cur[u];
+    }
+    for (; i < n; ++i) acc += s[i];
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll

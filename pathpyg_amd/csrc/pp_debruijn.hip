@@ -792,7 +792,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
 //                        order (fixed summation order, bit-reproducible); the fill pass starts every row at its task's prefix.
 // Sums: in-run weights and degrees are summed in (in-event, task) order — identical to the one-wave kernels and the generic path whenever
 // the partial sums are exactly representable (unit and integer-valued weights below 2^24), a different association of the same fp32 terms
-// otherwise (as the chunked reduction of long runs in pp_coalesce_*); with more than 64 out-events a merged weight is the sum, over the
+// otherwise (the one place where a builder's merged weights differ from PyG's left-to-right order below 2^24); with more than 64 out-events a merged weight is the sum, over the
 // successor's out-events in time order, of the weights of the instances each continues.
 struct Db2Hub {
     const uint8_t* flag;             // [n] kHubOut | kHubIn
@@ -922,7 +922,8 @@ __global__ __launch_bounds__(kBlock) void k_db2_hub_out_write(int64_t h_out, con
 }
 
 // step 4: merged first-order weight of every successor run at its head (0 elsewhere, as k_db2_out leaves them): run length, or the
-// left-to-right sum of the instance weights
+// left-to-right sum of the instance weights - once that fp32 sum reaches 2^24 (where the reference's sum of ones stalls) the float64 sum
+// rounded once, as run lengths are exact counts
 template <bool kW>
 __global__ __launch_bounds__(kBlock) void k_db2_hub_out_runs(int64_t h_out, const uint32_t* __restrict__ pos_s, const uint32_t* __restrict__ head,
                                                             const uint32_t* __restrict__ rank_s, const uint32_t* __restrict__ tkeys_s,
@@ -942,8 +943,13 @@ __global__ __launch_bounds__(kBlock) void k_db2_hub_out_runs(int64_t h_out, cons
     const uint32_t end = rs[rank_s[j] + 1u];
     if (!kW) { ow_s[p0 + within] = (float)(end - within); return; }
     float acc = 0.0f;
-    for (uint32_t x = within; x < end; ++x) acc += ow_s[p0 + x];          // (the run's own entries: nobody else touches them)
-    ow_s[p0 + within] = acc;
+    double exact = 0.0;
+    for (uint32_t x = within; x < end; ++x) {                             // (the run's own entries: nobody else touches them)
+        const float v = ow_s[p0 + x];
+        acc += v;
+        exact += (double)v;
+    }
+    ow_s[p0 + within] = fabsf(acc) < 16777216.f ? acc : (float)exact;
     for (uint32_t x = within + 1u; x < end; ++x) ow_s[p0 + x] = 0.0f;
 }
 
@@ -1016,7 +1022,8 @@ __global__ __launch_bounds__(kBlock) void k_db2_hub(int64_t n_tasks, int64_t del
         // ---- the in-runs that start in [qa, qb).  One virtual event behind the node's last in-event closes the last run: the run epilogue
         // exists once, inside the loop (a lambda over the kernel's argument structs would force them into scratch memory)
         uint32_t cur_a = 0u, cur_u = 0xFFFFFFFFu;
-        int ord = -1, hits = 0;
+        int ord = -1;
+        long long hits = 0;                  // (instances of one order-2 edge: an in-run of 2^25 events into 64 out-events passes 2^31)
         float facc = 0.0f, w1run = 0.0f, du_r = 0.0f, da_r = 0.0f;
         int32_t ob_r = 0;
         bool open = false, stop = qa >= qend;
@@ -1368,7 +1375,9 @@ __global__ __launch_bounds__(kBlock) void k_db2_hubx(int64_t n_tasks, int64_t de
                             }
                             const uint32_t rk = rkq[x] - (uint32_t)rbase;
                             if (c > 0 && j0 + l < g1 && rk < (uint32_t)kHubxRuns) {
-                                atomicAdd(&hist[rk], (uint32_t)c);
+                                // (an order-2 edge of 2^32 or more instances would wrap its count: the stream goes back to the caller)
+                                const uint32_t old_hits = atomicAdd(&hist[rk], (uint32_t)c);
+                                if (old_hits + (uint32_t)c < old_hits) atomicOr((unsigned long long*)a.status, (unsigned long long)kDb2Overflow);
                                 if (kW) atomicAdd(&histw[rk], wsum);
                                 pairs += c;
                             }
@@ -1388,14 +1397,14 @@ __global__ __launch_bounds__(kBlock) void k_db2_hubx(int64_t n_tasks, int64_t de
                     const int64_t rr = rbase + cc * kWave + l;
                     const bool valid = rr < R;
                     const uint32_t v = (uint32_t)(row0 + rr);
-                    const int hits = (int)hist[cc * kWave + l];
+                    const uint32_t hits = hist[cc * kWave + l];                 // (unsigned: an order-2 edge may have 2^31 instances)
                     hist[cc * kWave + l] = 0u;
                     float wgt = (float)hits;
                     if (kW) {
                         wgt = histw[cc * kWave + l];
                         histw[cc * kWave + l] = 0.0f;
                     }
-                    const bool emit = valid && hits > 0;
+                    const bool emit = valid && hits > 0u;
                     const uint64_t em = __ballot(emit);
                     const int reached = (int)__popcll(em);
                     const int odsel = slot == 0 ? od0 : (slot == 1 ? od1 : (slot == 2 ? od2 : od3));

@@ -301,29 +301,53 @@ __global__ __launch_bounds__(kBlock) void k_mo_sums1(const int32_t* __restrict__
     csum[t] = (int32_t)c;
 }
 
-// node pairs with very many events: one wave per pair, every lane a contiguous chunk left to right, chunks combined in lane order
+// Sums of fp32 weights that pass 2^24: the reference's left-to-right sum (PyG coalesce on CPU) stalls there (a sum of ones stops at 2^24,
+// a sum of threes drifts by one per add); beyond it the merged weight is the float64 sum rounded once, as run lengths are written as exact
+// counts.  Below 2^24 the left-to-right fp32 sum is kept bit for bit.
+__device__ __forceinline__ float mo_merged_weight(float ltr, double exact) { return fabsf(ltr) < 16777216.f ? ltr : (float)exact; }
+
+// node pairs with very many events: one wave per pair; the lanes gather kMoFold weights at a time into LDS in order and lane 0 folds them
+// left to right (fold_ltr: the gathers stay parallel, only the fp32 adds are serial); the float64 sum and the int64 continuation counts
+// are summed by the wave
+constexpr int kMoFold = 512;
 template <bool kWeighted>
 __global__ __launch_bounds__(kBlock) void k_mo_sums1_long(const int32_t* __restrict__ tptr, const uint4* __restrict__ inst, const int32_t* __restrict__ long_list,
                                                          const int32_t* __restrict__ long_count, float* __restrict__ w, int32_t* __restrict__ csum,
                                                          int64_t* __restrict__ status) {
+    __shared__ __attribute__((aligned(16))) float s_w[kWavesPerBlock][kWeighted ? kMoFold : 1];
+    float* sw = s_w[wave_id()];
     const int n_long = *long_count;
+    const int lane = lane_id();
     for (int g = blockIdx.x * kWavesPerBlock + wave_id(); g < n_long; g += gridDim.x * kWavesPerBlock) {
         const int32_t t = long_list[g];
         const int32_t x0 = tptr[t], x1 = tptr[t + 1];
-        const int32_t chunk = (x1 - x0 + kWave - 1) / kWave;
-        const int32_t b = x0 + lane_id() * chunk, e = b + chunk < x1 ? b + chunk : x1;
         float acc = 0.f;
+        double exact = 0.0;
         long long c = 0;
-        for (int32_t x = b; x < e; ++x) {
-            const uint4 it = inst[x];
-            acc += __uint_as_float(it.w);
-            c += (long long)(it.y & ~kHeadBit);
+        for (int32_t base = x0; base < x1; base += kMoFold) {
+            const int n = x1 - base < kMoFold ? x1 - base : kMoFold;
+#pragma unroll
+            for (int u = 0; u < kMoFold / kWave; ++u) {
+                const int i = u * kWave + lane;
+                if (i < n) {
+                    const uint4 it = inst[base + i];
+                    if (kWeighted) {
+                        sw[i] = __uint_as_float(it.w);
+                        exact += (double)__uint_as_float(it.w);
+                    }
+                    c += (long long)(it.y & ~kHeadBit);
+                }
+            }
+            if (kWeighted) {
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) fold_ltr<float>(sw, (uint32_t)n, acc);
+                __builtin_amdgcn_wave_barrier();
+            }
         }
-        float total = 0.f;
-        for (int l = 0; l < kWave; ++l) total += __shfl(acc, l, kWave);        // fixed order
         c = wave_sum<long long>(c);
-        if (lane_id() == 0) {
-            w[t] = kWeighted ? total : (float)(x1 - x0);
+        if (kWeighted) exact = wave_sum<double>(exact);
+        if (lane == 0) {
+            w[t] = kWeighted ? mo_merged_weight(acc, exact) : (float)(x1 - x0);
             if (c > 0x7fffffff) { atomicOr((unsigned long long*)status, (unsigned long long)kMoOverflow); c = 0x7fffffff; }
             csum[t] = (int32_t)c;
         }
@@ -628,6 +652,17 @@ __device__ __forceinline__ int32_t mo_find(const int32_t* __restrict__ cand, int
     return lo;
 }
 
+// the children of a new type (continuations of its instances) are counted in int64: 2^31 or more sets kMoOverflow (the caller falls back,
+// the refusal of k_mo_sums1 at level 1) and are clamped, so that the scan of the counts stays non-negative.  DEFENSIVE: no stream reaches
+// it while kMoBigMax^2 < 2^31.  A new type has at most kMoBigMax instances (its parent's children) and every instance at most kMoBigMax
+// continuations (the window of its last event, part of the children of that event's node pair at level 1); more children of one type
+// set kMoOverflow in k_mo_children_big of the same step, before the caller reads these counts.
+static_assert((int64_t)kMoBigMax * kMoBigMax < (int64_t)0x7fffffff, "the int32 children counts of k_mo_types* rely on kMoBigMax^2 < 2^31");
+__device__ __forceinline__ int32_t mo_children_count(int64_t c, int64_t* status) {
+    if (c > 0x7fffffff) { atomicOr((unsigned long long*)status, (unsigned long long)kMoOverflow); c = 0x7fffffff; }
+    return (int32_t)c;
+}
+
 // the new types of every parent type: instance range, last node, column (= id of the suffix type), merged weight, number of children.
 // One lane per parent type of class 0 (one instance, at most kMoSmall children: the types k_mo_children took); the others belong to
 // k_mo_types_wave / k_mo_types_big.  kLast: the top layer — only columns and weights are wanted
@@ -637,7 +672,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_types(int64_t n_types, const int3
                                                     const int32_t* __restrict__ cand_last, const void* __restrict__ child,
                                                     const int32_t* __restrict__ row_ptr, int32_t* __restrict__ tptr_out,
                                                     int32_t* __restrict__ tlast_out, int32_t* __restrict__ col_out, float* __restrict__ w_out,
-                                                    int32_t* __restrict__ csum_out, int all_wave) {
+                                                    int32_t* __restrict__ csum_out, int all_wave, int64_t* __restrict__ status) {
     const int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (s >= n_types) return;
     const int32_t c0 = ibase[s], n = ibase[s + 1] - c0;
@@ -657,12 +692,13 @@ __global__ __launch_bounds__(kBlock) void k_mo_types(int64_t n_types, const int3
     int32_t t = row_ptr[s] - 1;
     int32_t at = 0;                      // candidates below `at` are smaller than the current last node
     float acc = 0.f;
-    int32_t cnt = 0, cs = 0;
+    int32_t cnt = 0;
+    int64_t cs = 0;
 #pragma unroll
     for (int q = 0; q < kMoSmall; ++q) {
         if (q < n) {
             if (it[q].y & kHeadBit) {
-                if (cnt) { w_out[t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[t] = cs; }
+                if (cnt) { w_out[t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[t] = mo_children_count(cs, status); }
                 ++t;
                 acc = 0.f; cnt = 0; cs = 0;
                 const int32_t dd = (int32_t)it[q].z;
@@ -676,10 +712,10 @@ __global__ __launch_bounds__(kBlock) void k_mo_types(int64_t n_types, const int3
             }
             acc += __uint_as_float(it[q].w);
             ++cnt;
-            cs += (int32_t)(it[q].y & ~kHeadBit);
+            cs += (int64_t)(it[q].y & ~kHeadBit);
         }
     }
-    if (cnt) { w_out[t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[t] = cs; }
+    if (cnt) { w_out[t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[t] = mo_children_count(cs, status); }
 }
 
 // The same for the types of class 1 (k_mo_children_wave's), ONE WAVE PER 64 CONSECUTIVE TYPES, lanes = CHILD SLOTS in rounds of 64: the
@@ -699,7 +735,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
                                                          const void* __restrict__ child, const int32_t* __restrict__ row_ptr,
                                                          const uint8_t* __restrict__ cls, int32_t* __restrict__ tptr_out,
                                                          int32_t* __restrict__ tlast_out, int32_t* __restrict__ col_out, float* __restrict__ w_out,
-                                                         int32_t* __restrict__ csum_out, int all_wave) {
+                                                         int32_t* __restrict__ csum_out, int all_wave, int64_t* __restrict__ status) {
     __shared__ MoTypesLds lds[kWavesPerBlock];
     MoTypesLds& L = lds[wave_id()];
     const int lane = lane_id();
@@ -724,7 +760,8 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
     const int first_mid = __ffsll((long long)mids) - 1, last_mid = 63 - __clzll((long long)mids);
     const int32_t c_begin = L.cb[first_mid], c_end = L.cb[last_mid + 1];
     int32_t h_span = 0;                  // heads of the type that owns lane 0's slot, in earlier rounds
-    int32_t o_t = -1, o_cnt = 0, o_cs = 0;    // the open run: its type id, children so far, their children
+    int32_t o_t = -1, o_cnt = 0;          // the open run: its type id, children so far, their children (int64)
+    int64_t o_cs = 0;
     float o_acc = 0.f;
     for (int32_t cr = c_begin; cr < c_end; cr += kWave) {
         const int32_t c = cr + lane;
@@ -741,7 +778,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
         const uint64_t hb = __ballot(head);
         // close or extend the open run (lane 0 speaks for it)
         if (o_t >= 0 && !((acts & 1ull) && !(hb & 1ull))) {
-            if (lane == 0) { w_out[o_t] = kWeighted ? o_acc : (float)o_cnt; if (!kLast) csum_out[o_t] = o_cs; }
+            if (lane == 0) { w_out[o_t] = kWeighted ? o_acc : (float)o_cnt; if (!kLast) csum_out[o_t] = mo_children_count(o_cs, status); }
             o_t = -1;
         }
         if (acts == 0ull) { h_span = 0; continue; }
@@ -755,10 +792,10 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
         const int32_t t = act ? L.rp[lo] + (st < 0 ? h_span : 0) + (int32_t)__popcll(hb & lanemask_lt() & ~before_type) : 0;
         const bool owner = head || (lane == 0 && act);                        // (lane 0 without a head: the open run goes on)
         float acc = 0.f;
-        int32_t cs = 0;
+        int64_t cs = 0;
         if (owner) {
             if (!head) { acc = o_acc; cs = o_cs; }
-            for (int q = lane; q < run_end; ++q) { acc += __uint_as_float(L.w[q]); cs += (int32_t)L.cc[q]; }
+            for (int q = lane; q < run_end; ++q) { acc += __uint_as_float(L.w[q]); cs += (int64_t)L.cc[q]; }
         }
         const int32_t cnt = (owner && !head ? o_cnt : 0) + (run_end - lane);
         const int32_t my_t = head ? t : o_t;
@@ -788,10 +825,10 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
         const uint64_t owners = __ballot(owner);
         const int last_owner = 63 - __clzll((long long)owners);               // (owners != 0: the first active slot of a round is a head or lane 0)
         const bool reaches = __shfl(run_end, last_owner, kWave) == kWave;
-        if (owner && !(lane == last_owner && reaches)) { w_out[my_t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[my_t] = cs; }
+        if (owner && !(lane == last_owner && reaches)) { w_out[my_t] = kWeighted ? acc : (float)cnt; if (!kLast) csum_out[my_t] = mo_children_count(cs, status); }
         if (reaches) {
             o_t = __shfl(my_t, last_owner, kWave); o_acc = __shfl(acc, last_owner, kWave);
-            o_cs = __shfl(cs, last_owner, kWave); o_cnt = __shfl(cnt, last_owner, kWave);
+            o_cs = (int64_t)__shfl((long long)cs, last_owner, kWave); o_cnt = __shfl(cnt, last_owner, kWave);
         } else {
             o_t = -1;
         }
@@ -801,7 +838,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_wave(int64_t n_types, const
         h_span = (st_last < 0 ? h_span : 0) + (int32_t)__popcll(hb & ~before_last);
         __builtin_amdgcn_wave_barrier();
     }
-    if (o_t >= 0 && lane == 0) { w_out[o_t] = kWeighted ? o_acc : (float)o_cnt; if (!kLast) csum_out[o_t] = o_cs; }
+    if (o_t >= 0 && lane == 0) { w_out[o_t] = kWeighted ? o_acc : (float)o_cnt; if (!kLast) csum_out[o_t] = mo_children_count(o_cs, status); }
     __builtin_amdgcn_wave_barrier();
     }
 }
@@ -812,7 +849,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_big(const int32_t* __restri
                                                         const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ big_list,
                                                         const int32_t* __restrict__ big_count, int32_t* __restrict__ tptr_out,
                                                         int32_t* __restrict__ tlast_out, int32_t* __restrict__ col_out, float* __restrict__ w_out,
-                                                        int32_t* __restrict__ csum_out) {
+                                                        int32_t* __restrict__ csum_out, int64_t* __restrict__ status) {
     __shared__ uint32_t s_scratch[kWavesPerBlock + 1];
     const int n_big = *big_count;
     const int tid = threadIdx.x;
@@ -837,16 +874,17 @@ __global__ __launch_bounds__(kBlock) void k_mo_types_big(const int32_t* __restri
                 col_out[t] = bf + mo_find(cand_last + bf, 0, bc, dd);
                 if (!kLast) { tptr_out[t] = c0 + r; tlast_out[t] = dd; }
                 float acc = __uint_as_float(it.w);
-                int32_t cnt = 1, cs = (int32_t)(it.y & ~kHeadBit);
+                int32_t cnt = 1;
+                int64_t cs = (int64_t)(it.y & ~kHeadBit);
                 for (int32_t q = r + 1; q < n; ++q) {
                     const uint4 nx = mo_load_child<mo_fmt(kWeighted, kLast)>(child, c0 + q);
                     if (nx.y & kHeadBit) break;
                     acc += __uint_as_float(nx.w);
                     ++cnt;
-                    cs += (int32_t)(nx.y & ~kHeadBit);
+                    cs += (int64_t)(nx.y & ~kHeadBit);
                 }
                 w_out[t] = kWeighted ? acc : (float)cnt;
-                if (!kLast) csum_out[t] = cs;
+                if (!kLast) csum_out[t] = mo_children_count(cs, status);
             }
             ranks += total;
         }
@@ -1114,11 +1152,11 @@ int pp_multiorder_step(int64_t n_types, int64_t n_children, const int32_t* tptr,
 #define PP_MO_TYPES(W, L)                                                                                                                          \
     do {                                                                                                                                           \
         k_mo_types<W, L><<<grid, kBlock, 0, st>>>(n_types, tptr, ibase, col, cand_ptr, cand_last, child, row_ptr, tptr_out,                        \
-                                                  tlast_out, col_out, w_out, p.csum, all_wave);                                                              \
+                                                  tlast_out, col_out, w_out, p.csum, all_wave, p.result + 1);                                                \
         k_mo_types_wave<W, L><<<all_wave ? (unsigned)pieces : wave_grid, kBlock, 0, st>>>(                                                         \
-            n_types, ibase, col, cand_ptr, cand_last, child, row_ptr, p.cls, tptr_out, tlast_out, col_out, w_out, p.csum, all_wave);               \
+            n_types, ibase, col, cand_ptr, cand_last, child, row_ptr, p.cls, tptr_out, tlast_out, col_out, w_out, p.csum, all_wave, p.result + 1); \
         k_mo_types_big<W, L><<<1024, kBlock, 0, st>>>(ibase, col, cand_ptr, cand_last, child, row_ptr, p.big_list, p.counters,                     \
-                                                      tptr_out, tlast_out, col_out, w_out, p.csum);                                                \
+                                                      tptr_out, tlast_out, col_out, w_out, p.csum, p.result + 1);                                  \
     } while (0)
     if (weighted) { if (last) PP_MO_TYPES(true, true); else PP_MO_TYPES(true, false); }
     else { if (last) PP_MO_TYPES(false, true); else PP_MO_TYPES(false, false); }

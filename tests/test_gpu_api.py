@@ -247,8 +247,8 @@ def test_fuzz_from_temporal_graph_against_oracle(pp):
             for key in ("edge_index", "node_sequence", "inverse_idx"):
                 assert torch.equal(d[key].cpu(), want[k][key]), (case, m, n, span, K, delta, float_time, k, key)
             if not torch.equal(d.edge_weight.cpu(), want[k]["edge_weight"]):
-                # runs of > 512 parallel edges are summed by a tree, not left to right: once the fp32 partial sums pass 2^24 the
-                # reference's sequential accumulation is the LESS accurate one - then the float64 evaluation decides
+                # once a fp32 sum passes 2^24 the reference's sequential accumulation stalls and the kernels write the float64 sum
+                # rounded once (merged weights): then the float64 evaluation decides
                 if exact is None:
                     exact = om.layers_from_temporal(sei, st, n, delta=delta, max_order=K, edge_weight=w[perm].double(), cached=cached)
                 assert float(want[k]["edge_weight"].max()) > 2 ** 24, (case, k)
