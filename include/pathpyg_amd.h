@@ -223,6 +223,36 @@ int pp_multiorder_step(int64_t n_types, int64_t n_children, const int32_t* tptr,
                        const int32_t* cand_ptr, const int32_t* cand_last, const void* tab, int weighted, int last, void* child, int32_t* row_ptr,
                        int32_t* tptr_out, int32_t* ibase_out, int32_t* tlast_out, int32_t* col_out, float* w_out, void* ws, size_t ws_bytes,
                        pp_stream_t stream);
+/* The same layers on N ranks, split by FIRST NODE (the reference builds them on one device only: MultiOrderModel.from_temporal_graph,
+ * src/pathpyG/core/multi_order_model.py:124-192, per order iterate_lift_order :83-122).  Types are in lexicographic order of their node
+ * sequences and a child keeps its parent's first node, so the rank that owns the first-order nodes [node_lo, node_hi) as first nodes owns a
+ * contiguous block of types at every level = a contiguous block of rows of every layer.  The stream and pp_temporal_windows are replicated.
+ *
+ * pp_multiorder_node_loads: what the cuts are chosen from, right after pp_temporal_windows (`lift_ws`).  loads [2, num_nodes + 1] int64:
+ *   loads[0][v] = out-events of the nodes below v (= v's first position in the source-grouped list), loads[1][v] = level-2 instances that
+ *   start at a node below v (sum of their events' window counts); loads[.][num_nodes] are the totals.
+ * pp_multiorder_prepare_range: pp_multiorder_prepare for the events whose source lies in [node_lo, node_hi) — the list positions
+ *   [p_lo, p_lo + m_own) with p_lo = loads[0][node_lo], m_own = loads[0][node_hi] - p_lo > 0.  inst / tptr / ibase / tlast / w have capacity
+ *   m_own (tptr / ibase: m_own + 1) and are numbered from 0 on the rank; rowptr [node_hi - node_lo + 1] is the owned slice of layer 1's row
+ *   pointers as offsets into the rank's own edges; tlast holds global node ids; `tab` [m] covers the whole stream (children end anywhere).
+ *   ws: pp_multiorder_prepare_range_ws_bytes(m, m_own); the result header and the status bits are pp_multiorder_prepare's, bit 4 = a node of
+ *   the range with more than 4096 out-events: call again with radix_sort != 0 (one stable radix sort of the rank's events by (source, target)).
+ *   With [0, num_nodes) the outputs are pp_multiorder_prepare's, bit for bit.
+ * pp_multiorder_step then runs unchanged on a rank's types with tptr / ibase of the rank and col / cand_ptr / cand_last GLOBAL: it writes
+ *   global columns.
+ * pp_multiorder_stitch: cand_ptr [rows + 1] / cand_last [edges] of the next step from the all-gathered pieces, one launch.  `gathered` holds
+ *   `world` blocks of `stride` int32; block r = the row pointers of rank r's rows (row_lo[r+1] - row_lo[r] entries, offsets into its own
+ *   edges) and, from entry `last_at` on, the last nodes of its edges (edge_lo[r+1] - edge_lo[r] entries).  row_lo / edge_lo: HOST arrays
+ *   [world + 1] of the ranks' first global row / edge, world <= 128.  cand_ptr[i] = piece entry + edge_lo[rank], cand_ptr[rows] = edges. */
+size_t pp_multiorder_node_loads_ws_bytes(int64_t m);
+int pp_multiorder_node_loads(int64_t m, int64_t num_nodes, void* lift_ws, size_t lift_ws_bytes, int64_t* loads, void* ws, size_t ws_bytes,
+                             pp_stream_t stream);
+size_t pp_multiorder_prepare_range_ws_bytes(int64_t m, int64_t m_own);
+int pp_multiorder_prepare_range(const int64_t* edge_index, int64_t m, int64_t num_nodes, const float* weight, void* lift_ws, size_t lift_ws_bytes,
+                                int64_t node_lo, int64_t node_hi, int64_t p_lo, int64_t m_own, int radix_sort, void* tab, void* inst, int32_t* tptr,
+                                int32_t* ibase, int32_t* tlast, float* w, int32_t* rowptr, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_multiorder_stitch(const int32_t* gathered, int64_t stride, int64_t last_at, int world, const int64_t* row_lo, const int64_t* edge_lo,
+                         int32_t* cand_ptr, int32_t* cand_last, pp_stream_t stream);
 
 /* ------------------------------------------------------------------ order lifts (pp_lift.hip) */
 

@@ -7,6 +7,7 @@ happens in the HIP kernels.  There is no CPU implementation behind these calls.
 """
 from __future__ import annotations
 
+import ctypes
 import threading
 
 import torch
@@ -971,39 +972,161 @@ def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
             return None                  # (unsorted: the caller sorts and takes the generic path; 2^31 continuations of one node pair's events)
         if event_graph is not None and children != n_list:      # the instances of level 2 ARE the event graph's edges
             return None
+        level = MultiOrderLevel(types=types, children=children, status=status, tptr=tptr, ibase=ibase, inst=inst, row_ptr=row_ptr, col=tlast,
+                                weight=w, tlast=tlast)
         layers = [MultiOrderLayer(n_nodes=n, n_edges=types, n_instances=m, row_ptr=row_ptr, col=tlast[:types], weight=w[:types], last=tlast[:types])]
-        col, cand_ptr, cand_last = tlast, row_ptr, tlast
+        cand_ptr, cand_last = row_ptr, tlast
         for k in range(2, max_order + 1):
-            if types == 0 or children == 0 or children >= _INT32_ROWS:
+            if level.types == 0 or level.children == 0 or level.children >= _INT32_ROWS:
                 return None
             last = k == max_order
-            child = torch.empty((children, (1 if weight is None else 2) if last else 4), **i32)      # (the top layer's children are nobody's parents)
-            row_next = torch.empty(types + 1, **i32)
-            col_next, w_next = torch.empty(children, **i32), torch.empty(children, **f32)
-            tptr_next = ibase_next = tlast_next = None
-            if not last:
-                tptr_next, ibase_next, tlast_next = torch.empty(children + 1, **i32), torch.empty(children + 1, **i32), torch.empty(children, **i32)
-            ws = _workspace(L.pp_multiorder_step_ws_bytes(types, children), dev)
-            t0 = tick()
-            check(L.pp_multiorder_step(types, children, _p(tptr), _p(ibase), _p(col), _p(inst), _p(cand_ptr), _p(cand_last), _p(tab),
-                                       0 if weight is None else 1, 1 if last else 0, _p(child), _p(row_next), _p(tptr_next), _p(ibase_next),
-                                       _p(tlast_next), _p(col_next), _p(w_next), _p(ws), ws.numel(), _stream()), "pp_multiorder_step")
-            if clock is not None:
-                clock.append((f"layer {k}", t0, tick()))
-            new_types, status, new_children, _ = ws[:32].view(torch.int64).tolist()
-            del ws
-            if status & 4:
+            nxt = _multi_order_step(level, cand_ptr, cand_last, tab, weight is not None, last, clock, f"layer {k}")
+            if nxt.status & 4:
                 return None
-            if 2 * new_types < children:                    # far fewer types than instances: do not keep the instance-sized buffers alive
-                col_next, w_next = col_next[:new_types].clone(), w_next[:new_types].clone()
-                if not last:
-                    tlast_next = tlast_next[:new_types].clone()
-            layers.append(MultiOrderLayer(n_nodes=types, n_edges=new_types, n_instances=children, row_ptr=row_next, col=col_next[:new_types],
-                                          weight=w_next[:new_types], last=None if last else tlast_next[:new_types]))
-            tptr, ibase, col, inst = tptr_next, ibase_next, col_next, child
-            cand_ptr, cand_last = row_next, tlast_next
-            types, children = new_types, new_children
+            layers.append(MultiOrderLayer(n_nodes=level.types, n_edges=nxt.types, n_instances=level.children, row_ptr=nxt.row_ptr, col=nxt.col[:nxt.types],
+                                          weight=nxt.weight[:nxt.types], last=None if last else nxt.tlast[:nxt.types]))
+            cand_ptr, cand_last = nxt.row_ptr, nxt.tlast
+            level = nxt
     return layers
+
+
+class MultiOrderLevel:
+    """Level k of the level-by-level builder on the device, with layer k as it left the kernels: ``types`` types (= edges of layer k) with
+    ``children`` instances at level k + 1 (both on the host, with ``status``, from the level's one read-back); ``tptr`` / ``ibase`` [types + 1],
+    ``inst`` the level's instance records, ``tlast`` [types] the types' last nodes (``None`` for the top layer); layer k's ``row_ptr`` (over ITS
+    nodes), ``col`` and ``weight`` (capacity >= types).  On a rank of the split by first node ``tptr`` / ``ibase`` / ``row_ptr`` are numbered from
+    0 on the rank, ``col`` holds global ids."""
+
+    __slots__ = ("types", "children", "status", "tptr", "ibase", "inst", "row_ptr", "col", "weight", "tlast")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def multi_order_step(level: MultiOrderLevel, cand_ptr: torch.Tensor, cand_last: torch.Tensor, tab: torch.Tensor, weighted: bool, last: bool,
+                     clock: list | None = None, name: str = "layer") -> MultiOrderLevel:
+    """Level k + 1 (and layer k + 1) from ``level`` = level k with ``types > 0`` types and ``children > 0`` children (pp_multiorder_step; one
+    read-back).  ``cand_ptr`` / ``cand_last``: row pointers of layer k over ALL its nodes and the last nodes of ALL its edges — the tables a new
+    edge's column ``suffix(s) ++ d`` is looked up in; the columns written are positions in them, so with the global tables a rank's own types
+    (``tptr`` / ``ibase`` numbered from 0 on the rank) yield global columns.  ``last``: the top layer (no next level is kept).  Status bit 2:
+    a type with more than 4096 children, the outputs are incomplete."""
+    with torch.cuda.device(level.tptr.device):
+        return _multi_order_step(level, cand_ptr, cand_last, tab, weighted, last, clock, name)
+
+
+def _multi_order_step(level: MultiOrderLevel, cand_ptr, cand_last, tab, weighted: bool, last: bool, clock, name: str) -> MultiOrderLevel:
+    """:func:`multi_order_step` under the caller's device guard (:func:`multi_order_temporal` holds one over all its levels)."""
+    dev = level.tptr.device
+    types, children = level.types, level.children
+    L = lib()
+    i32 = dict(dtype=torch.int32, device=dev)
+    f32 = dict(dtype=torch.float32, device=dev)
+    child = torch.empty((children, (2 if weighted else 1) if last else 4), **i32)      # (the top layer's children are nobody's parents)
+    row_next = torch.empty(types + 1, **i32)
+    col_next, w_next = torch.empty(children, **i32), torch.empty(children, **f32)
+    tptr_next = ibase_next = tlast_next = None
+    if not last:
+        tptr_next, ibase_next, tlast_next = torch.empty(children + 1, **i32), torch.empty(children + 1, **i32), torch.empty(children, **i32)
+    ws = _workspace(L.pp_multiorder_step_ws_bytes(types, children), dev)
+    t0 = None
+    if clock is not None:
+        t0 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+    check(L.pp_multiorder_step(types, children, _p(level.tptr), _p(level.ibase), _p(level.col), _p(level.inst), _p(cand_ptr), _p(cand_last), _p(tab),
+                               1 if weighted else 0, 1 if last else 0, _p(child), _p(row_next), _p(tptr_next), _p(ibase_next),
+                               _p(tlast_next), _p(col_next), _p(w_next), _p(ws), ws.numel(), _stream()), "pp_multiorder_step")
+    if clock is not None:
+        t1 = torch.cuda.Event(enable_timing=True)
+        t1.record()
+        clock.append((name, t0, t1))
+    new_types, status, new_children, _ = ws[:32].view(torch.int64).tolist()
+    del ws
+    if not status & 4 and 2 * new_types < children:                    # far fewer types than instances: do not keep the instance-sized buffers alive
+        col_next, w_next = col_next[:new_types].clone(), w_next[:new_types].clone()
+        if not last:
+            tlast_next = tlast_next[:new_types].clone()
+    return MultiOrderLevel(types=new_types, children=new_children, status=status, tptr=tptr_next, ibase=ibase_next, inst=child, row_ptr=row_next,
+                           col=col_next, weight=w_next, tlast=tlast_next)
+
+
+def multi_order_node_loads(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delta, weight: torch.Tensor | None = None):
+    """First step of the split by first node (:func:`pathpyg_amd.distributed.build_multi_order_shard`) on a replicated TIME-SORTED stream: the
+    windows pass (pp_temporal_windows, whole stream) and the per-node loads the cuts are chosen from (pp_multiorder_node_loads).  Returns
+    ``(windows, loads)``: ``windows`` is what :func:`multi_order_prepare_range` takes, ``loads`` int64 [2, num_nodes + 1] stays on the device —
+    ``loads[0][v]`` = out-events of the nodes below v, ``loads[1][v]`` = level-2 instances that start at a node below v.  No read-back.
+    ``None``: a stream the level-by-level builder does not take (empty, 2^31 events, not sorted by time, a weight that is not float32,
+    tensors on the host)."""
+    ei = _edge_index(edge_index)
+    if not ei.is_cuda or not time.is_cuda or (weight is not None and not weight.is_cuda):
+        return None
+    dev = require_device(ei, time, weight)
+    stream = _event_stream(ei, time, weight)
+    m, n = ei.size(1), int(num_nodes)
+    if stream is None or m == 0 or n == 0 or m >= _INT32_ROWS:
+        return None
+    time, weight = stream
+    if not is_sorted(time):              # (one cheap kernel instead of the windows pass; replicated input: every rank decides alike)
+        return None
+    kind, di, df = resolve_delta(time.dtype, delta)
+    L = lib()
+    with torch.cuda.device(dev):
+        lift_ws = _workspace(L.pp_temporal_ws_bytes(m, n), dev)
+        check(L.pp_temporal_windows(_p(ei), _p(time), _DTYPE_CODE[time.dtype], m, n, kind, di, df, _p(lift_ws), lift_ws.numel(), _stream()),
+              "pp_temporal_windows")
+        loads = torch.empty((2, n + 1), dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_multiorder_node_loads_ws_bytes(m), dev)
+        check(L.pp_multiorder_node_loads(m, n, _p(lift_ws), lift_ws.numel(), _p(loads), _p(ws), ws.numel(), _stream()), "pp_multiorder_node_loads")
+    return (ei, weight, n, lift_ws), loads
+
+
+def multi_order_prepare_range(windows, node_lo: int, node_hi: int, p_lo: int, m_own: int):
+    """Level 1 of the events whose source lies in ``[node_lo, node_hi)`` (pp_multiorder_prepare_range): ``windows`` from
+    :func:`multi_order_node_loads`, ``p_lo = loads[0][node_lo]``, ``m_own = loads[0][node_hi] - p_lo > 0``.  Returns ``(level, tab)``: the
+    rank's :class:`MultiOrderLevel` 1 (``row_ptr`` = the owned slice of layer 1's row pointers as offsets into the rank's own edges, ``col`` =
+    ``tlast`` = global node ids; ``status`` bits 0 / 1 / 2 as pp_multiorder_prepare) and the continuation table of the WHOLE stream.  A node of
+    the range with more than 4096 out-events sends the rank's events to the radix sort (second call); one read-back per call."""
+    ei, weight, n, lift_ws = windows
+    dev = ei.device
+    m, n_own = ei.size(1), int(node_hi) - int(node_lo)
+    L = lib()
+    with torch.cuda.device(dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        tab = torch.empty((m, 4), **i32)
+        inst = torch.empty((m_own, 4), **i32)
+        tptr, ibase = torch.empty(m_own + 1, **i32), torch.empty(m_own + 1, **i32)
+        tlast, w = torch.empty(m_own, **i32), torch.empty(m_own, **f32)
+        row_ptr = torch.empty(n_own + 1, **i32)
+        ws = _workspace(L.pp_multiorder_prepare_range_ws_bytes(m, m_own), dev)
+        for radix in ((True,) if m_own > 1024 * n_own else (False, True)):
+            check(L.pp_multiorder_prepare_range(_p(ei), m, n, _p(weight), _p(lift_ws), lift_ws.numel(), int(node_lo), int(node_hi), int(p_lo), int(m_own),
+                                                1 if radix else 0, _p(tab), _p(inst), _p(tptr), _p(ibase), _p(tlast), _p(w), _p(row_ptr), _p(ws), ws.numel(),
+                                                _stream()), "pp_multiorder_prepare_range")
+            types, status, children, _ = ws[:32].view(torch.int64).tolist()
+            if not status & 16:
+                break
+    return MultiOrderLevel(types=types, children=children, status=status & ~16, tptr=tptr, ibase=ibase, inst=inst, row_ptr=row_ptr, col=tlast,
+                           weight=w, tlast=tlast), tab
+
+
+def multi_order_stitch(gathered: torch.Tensor, stride: int, last_at: int, row_lo: list[int], edge_lo: list[int]):
+    """``(cand_ptr int32 [rows + 1], cand_last int32 [edges])`` of the next step from the all-gathered per-rank pieces, one launch
+    (pp_multiorder_stitch): ``gathered`` int32 [world * stride], block r = rank r's row pointers (offsets into its own edges) and, from entry
+    ``last_at`` on, the last nodes of its edges; ``row_lo`` / ``edge_lo`` [world + 1]: first global row / edge of every rank."""
+    dev = require_device(gathered)
+    world = len(row_lo) - 1
+    if gathered.dtype != torch.int32 or gathered.numel() < world * stride:
+        raise ValueError("multi_order_stitch: `gathered` must hold world * stride int32")
+    gathered = gathered.contiguous()
+    with torch.cuda.device(dev):
+        cand_ptr = torch.empty(int(row_lo[-1]) + 1, dtype=torch.int32, device=dev)
+        cand_last = torch.empty(int(edge_lo[-1]), dtype=torch.int32, device=dev)
+        rows = (ctypes.c_int64 * (world + 1))(*[int(v) for v in row_lo])
+        edges = (ctypes.c_int64 * (world + 1))(*[int(v) for v in edge_lo])
+        check(lib().pp_multiorder_stitch(_p(gathered), int(stride), int(last_at), world, rows, edges, _p(cand_ptr), _p(cand_last), _stream()),
+              "pp_multiorder_stitch")
+    return cand_ptr, cand_last
 
 
 class DeBruijn2Part:

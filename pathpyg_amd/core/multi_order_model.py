@@ -410,14 +410,16 @@ def _fast_stream(g: TemporalGraph, weight: str):
     return ei, time, w, n, m
 
 
-def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, weight2=None, inverse_high=None) -> dict:
+def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, weight2=None, inverse_high=None, gather_concat=None) -> dict:
     """The layers a fast build keeps (all, or with ``cached=False`` the top one) as :class:`~pathpyg_amd.data.Lazy` views of its source-major
     CSR arrays, ``csr[k - 1]`` = layer k (:class:`~pathpyg_amd._hip.MultiOrderLayer`), identical to what the generic kernels produce, made when
     somebody reads them (reference multi_order_model.py:153-191): ``edge_index`` = (row of every CSR entry, column); ``node_sequence`` of layer 1
     = ``arange(n)``, of layer k the sequence of the entry's row in layer k-1 followed by the entry's last node (De Bruijn property: the nodes of
     layer k ARE the edges of layer k-1; for layer 2 that is layer 1's edge itself); ``inverse_idx`` of layer 1 = ``arange(n)``, of layer 2 the
     merged first-order edge of every event, from layer 3 on ``inverse_high(k)``.  ``weight2(edge_index)``: layer 2's merged weights, for a
-    builder that does not keep them in the layer's edge order."""
+    builder that does not keep them in the layer's edge order.  ``gather_concat``: what extends the node sequences (default: the HIP kernel
+    behind ``_dispatch.gather_concat``; ``distributed.gather_multi_order`` hands its ``ops``' on)."""
+    gather_concat = _dispatch.gather_concat if gather_concat is None else gather_concat
     # (the makers capture CSR arrays, plans and other Lazy objects, never the Data bags that hold them: a bag -> Lazy -> closure -> bag cycle would
     #  keep ~4 GB of plans per model alive until the cyclic collector runs — measured: 14.0 -> 20.8 ms per API step from the 11th step on)
     n, dev = csr[0].n_nodes, ei.device
@@ -444,7 +446,7 @@ def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, wei
         else:
             def seq_of(prev_index=prev_index, prev_seq=prev_seq, last=csr[k - 2].last):
                 # node u of layer k = edge u of layer k-1: the sequence of that edge's source node, then the edge's last node
-                return _dispatch.gather_concat(prev_seq.resolve(), prev_index.resolve()[0].contiguous(), last.long())
+                return gather_concat(prev_seq.resolve(), prev_index.resolve()[0].contiguous(), last.long())
 
             seq = Lazy(seq_of, (b.n_nodes, k))
             inverse = Lazy(lambda k=k: inverse_high(k), (csr[k - 2].n_instances,))

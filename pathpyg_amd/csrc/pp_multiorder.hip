@@ -140,7 +140,7 @@ struct MoListLds {
 __global__ __launch_bounds__(kBlock) void k_mo_lists_wave(int64_t n_nodes, const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids,
                                                          const uint4* __restrict__ ev, uint4* __restrict__ inst, int32_t* __restrict__ head,
                                                          uint4* __restrict__ tab, int32_t* __restrict__ big_list, int32_t* __restrict__ counters,
-                                                         int64_t* __restrict__ status) {
+                                                         int64_t* __restrict__ status, int32_t pbase) {
     __shared__ MoListLds lds[kWavesPerBlock];
     MoListLds& L = lds[wave_id()];
     const int lane = lane_id();
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_wave(int64_t n_nodes, const
                         const int32_t at = L.p0s[lo] + (slot - (L.pre[lo] - base));
                         const uint32_t e = ids[at];
                         const uint4 r = ev[e];
-                        tab[at] = make_uint4(r.x, r.y, r.z, e);          // (the window table's entry of this list position: k_mo_tab's gather, already here)
+                        if (tab) tab[at] = make_uint4(r.x, r.y, r.z, e);  // (the window table's entry of this list position: k_mo_tab's gather, already here)
                         L.cf[slot] = r.y; L.cc[slot] = r.z; L.w[slot] = r.w;
                         key = ((uint64_t)lo << 40) | ((uint64_t)r.x << 8) | (uint64_t)slot;
                     }
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_wave(int64_t n_nodes, const
                     const uint64_t prev = pos ? L.keys[pos - 1] : ~0ull;
                     const bool h = (key >> 8) != (prev >> 8);                  // another node or another target
                     const int nl = (int)(key >> 40), slot = (int)(key & 0xffu);
-                    const int32_t at = L.p0s[nl] + (pos - (L.pre[nl] - base));
+                    const int32_t at = L.p0s[nl] + (pos - (L.pre[nl] - base)) - pbase;
                     inst[at] = make_uint4(L.cf[slot], L.cc[slot] | (h ? kHeadBit : 0u), (uint32_t)(key >> 8), L.w[slot]);
                     head[at] = h ? 1 : 0;
                 }
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_wave(int64_t n_nodes, const
 
 __global__ __launch_bounds__(kBlock) void k_mo_lists_big(const uint32_t* __restrict__ rowptr, const uint32_t* __restrict__ ids, const uint4* __restrict__ ev,
                                                         uint4* __restrict__ inst, int32_t* __restrict__ head, uint4* __restrict__ tab,
-                                                        const int32_t* __restrict__ big_list, const int32_t* __restrict__ counters) {
+                                                        const int32_t* __restrict__ big_list, const int32_t* __restrict__ counters, int32_t pbase) {
     __shared__ uint64_t s_key[kMoBigMax];
     const int n_big = counters[1];
     const int tid = threadIdx.x;
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_big(const uint32_t* __restr
             if (c < n) {
                 const uint32_t e = ids[p0 + c];
                 const uint4 r = ev[e];
-                tab[p0 + c] = make_uint4(r.x, r.y, r.z, e);
+                if (tab) tab[p0 + c] = make_uint4(r.x, r.y, r.z, e);
                 key = ((uint64_t)r.x << 32) | (uint64_t)c;
             }
             s_key[c] = key;
@@ -261,8 +261,8 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_big(const uint32_t* __restr
             const uint32_t dd = (uint32_t)(key >> 32);
             const bool h = r == 0 || (uint32_t)(s_key[r - 1] >> 32) != dd;
             const uint4 e = ev[ids[p0 + (int32_t)(uint32_t)key]];
-            inst[p0 + r] = make_uint4(e.y, e.z | (h ? kHeadBit : 0u), dd, e.w);
-            head[p0 + r] = h ? 1 : 0;
+            inst[p0 - pbase + r] = make_uint4(e.y, e.z | (h ? kHeadBit : 0u), dd, e.w);
+            head[p0 - pbase + r] = h ? 1 : 0;
         }
         __syncthreads();
     }
@@ -271,9 +271,9 @@ __global__ __launch_bounds__(kBlock) void k_mo_lists_big(const uint32_t* __restr
 // types of level 1 from the instances in place: instance range, last node; row pointers over the first-order nodes = heads before a node's list
 __global__ __launch_bounds__(kBlock) void k_mo_types1_lists(const uint4* __restrict__ inst, const int32_t* __restrict__ head_before, const uint32_t* __restrict__ list_ptr,
                                                            int64_t m, int64_t n, int32_t* __restrict__ tptr, int32_t* __restrict__ tlast,
-                                                           int32_t* __restrict__ rowptr) {
+                                                           int32_t* __restrict__ rowptr, uint32_t pbase) {
     const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j <= n) rowptr[j] = head_before[list_ptr[j]];
+    if (j <= n) rowptr[j] = head_before[list_ptr[j] - pbase];
     if (j >= m) return;
     const int32_t t = head_before[j];
     if (head_before[j + 1] != t) { tptr[t] = (int32_t)j; tlast[t] = (int32_t)inst[j].z; }
@@ -935,6 +935,95 @@ static MoGraphWs carve_mo_graph(void* ws, int64_t m, int64_t e2) {
     return w;
 }
 
+// ------------------------------------------------------------------ the split by first node (pp_multiorder_node_loads / _prepare_range / _stitch)
+// A rank that owns the first-order nodes [node_lo, node_hi) as FIRST nodes owns a contiguous block of types at every level (types are in
+// lexicographic order of their node sequences), i.e. a contiguous block of rows of every layer with all their out-edges.  Its events are
+// the positions [p_lo, p_hi) of the source-grouped list of pp_temporal_windows; everything of level 1 is numbered from 0 on the rank.
+
+// continuation count of the event at every position of the source-grouped list (its prefix sums are the level-2 loads of the nodes)
+__global__ __launch_bounds__(kBlock) void k_mo_list_counts(const uint32_t* __restrict__ ids, const int32_t* __restrict__ count, int64_t m,
+                                                          int32_t* __restrict__ out) {
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p < m) out[p] = count[ids[p]];
+}
+// loads[0][v] = out-events of the nodes below v, loads[1][v] = level-2 instances that start at a node below v   (v = 0 .. n)
+__global__ __launch_bounds__(kBlock) void k_mo_node_loads(const uint32_t* __restrict__ rowptr, const int64_t* __restrict__ pos_prefix, int64_t n,
+                                                         int64_t* __restrict__ loads) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v > n) return;
+    const uint32_t p = rowptr[v];
+    loads[v] = (int64_t)p;
+    loads[n + 1 + v] = pos_prefix[p];
+}
+// (source - node_lo, target) keys of the rank's own events in list order (grouped by source, time order inside): the radix route of a range
+template <typename KeyT>
+__global__ __launch_bounds__(kBlock) void k_mo_key_pair_range(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, const uint32_t* __restrict__ ids,
+                                                             int64_t m_own, int64_t node_lo, int64_t n_own, int64_t n, int bits, KeyT* __restrict__ keys) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= m_own) return;
+    const uint32_t e = ids[j];
+    int64_t a = src[e] - node_lo, b = dst[e];
+    if (a < 0 || a >= n_own) a = 0;        // (cannot happen for a list range of these nodes; nothing here may run off an array)
+    if (b < 0 || b >= n) b = 0;
+    keys[j] = ((KeyT)a << bits) | (KeyT)b;
+}
+
+// cand_ptr / cand_last of the next step from the all-gathered pieces: rank r's block of `gathered` (`stride` entries) holds the row pointers
+// of its rows (offsets into ITS edges) and, from entry `last_at` on, the last nodes of its edges.  One thread per output entry; its rank by
+// bisection over the (at most kMoMaxWorld + 1) bounds that travel as kernel arguments.
+constexpr int kMoMaxWorld = 128;
+struct MoStitch {
+    int32_t row_lo[kMoMaxWorld + 1], edge_lo[kMoMaxWorld + 1];
+    int world;
+};
+__device__ __forceinline__ int mo_rank_of(const int32_t* lo, int world, int32_t i) {      // last rank whose range starts at or before i
+    int a = 0, b = world;
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (lo[mid] <= i) a = mid; else b = mid;
+    }
+    return a;
+}
+__global__ __launch_bounds__(kBlock) void k_mo_stitch(const int32_t* __restrict__ gathered, int64_t stride, int64_t last_at, const MoStitch st,
+                                                     int32_t* __restrict__ cand_ptr, int32_t* __restrict__ cand_last) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t rows = st.row_lo[st.world], edges = st.edge_lo[st.world];
+    if (i < rows) {
+        const int r = mo_rank_of(st.row_lo, st.world, (int32_t)i);
+        cand_ptr[i] = gathered[(int64_t)r * stride + (i - st.row_lo[r])] + st.edge_lo[r];
+    } else if (i == rows) {
+        cand_ptr[rows] = (int32_t)edges;
+    } else if (i - rows - 1 < edges) {
+        const int64_t e = i - rows - 1;
+        const int r = mo_rank_of(st.edge_lo, st.world, (int32_t)e);
+        cand_last[e] = gathered[(int64_t)r * stride + last_at + (e - st.edge_lo[r])];
+    }
+}
+
+struct MoLoadsWs {
+    int32_t* counts;          // [m] continuation count per list position
+    int64_t* prefix;          // [m + 1]
+    int64_t* total;
+    void* scratch;
+    size_t scratch_bytes, total_bytes;
+};
+static MoLoadsWs carve_mo_loads(void* ws, int64_t m) {
+    Arena a(ws, (size_t)-1);
+    MoLoadsWs w;
+    w.total = a.take<int64_t>(2);
+    w.counts = a.take<int32_t>(m);
+    w.prefix = a.take<int64_t>(m + 1);
+    w.scratch_bytes = scan_ws_bytes(m + 1);
+    w.scratch = a.take<char>((int64_t)w.scratch_bytes);
+    w.total_bytes = a.used;
+    return w;
+}
+
+// the node range of a pp_multiorder_prepare_range call: nodes [node_lo, node_lo + n_own), list positions [p_lo, p_lo + m_own)
+struct MoRange {
+    int64_t node_lo, n_own, p_lo, m_own;
+};
+
 struct MoPrepWs {
     int64_t* result;          // {types of level 1, status, children of level 1 (= E2), node pairs with long runs}
     void *keys_a, *keys_b;    // (source, target) keys before / after the sort: uint32 or uint64 [m]
@@ -945,14 +1034,15 @@ struct MoPrepWs {
     size_t scratch_bytes, total_bytes;
 };
 
-static MoPrepWs carve_mo_prep(void* ws, int64_t m) {
+// m: the events level 1 is built from (a rank's own); m_ev: the events of the whole stream (`ev` covers all: children end anywhere)
+static MoPrepWs carve_mo_prep(void* ws, int64_t m, int64_t m_ev) {
     Arena a(ws, (size_t)-1);
     MoPrepWs w;
     w.result = a.take<int64_t>(4);
     w.keys_a = a.take<uint64_t>(m);
     w.keys_b = a.take<uint64_t>(m);
     w.perm = a.take<uint32_t>(m);
-    w.ev = a.take<uint4>(m);
+    w.ev = a.take<uint4>(m_ev);
     w.head = a.take<int32_t>(m);
     w.head_before = a.take<int32_t>(m + 1);
     w.csum = a.take<int32_t>(m);
@@ -983,6 +1073,26 @@ static int mo_level1(const MoPrepWs& p, const TemporalLists& tl, const int64_t* 
     rc = exclusive_scan<int32_t, int32_t>(p.head, m, p.head_before, true, p.result, p.scratch, p.scratch_bytes, st);
     if (rc != PP_OK) return rc;
     k_mo_types1<KeyT><<<grid, kBlock, 0, st>>>(sorted, bits, p.head_before, m, num_nodes, tptr, tlast, rowptr);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+// the same on a rank's own events: ONE stable sort of its list range (grouped by source, time order inside) by the (source, target) key
+template <typename KeyT>
+static int mo_level1_range(const MoPrepWs& p, const TemporalLists& tl, const int64_t* src, const int64_t* dst, const MoRange& rg, int64_t num_nodes,
+                           int bits, uint4* inst, int32_t* tptr, int32_t* tlast, int32_t* rowptr, hipStream_t st) {
+    const unsigned grid = (unsigned)ceil_div(rg.m_own, kBlock);
+    KeyT* keys = (KeyT*)p.keys_a;
+    KeyT* sorted = (KeyT*)p.keys_b;
+    k_mo_key_pair_range<KeyT><<<grid, kBlock, 0, st>>>(src, dst, tl.ids + rg.p_lo, rg.m_own, rg.node_lo, rg.n_own, num_nodes, bits, keys);
+    PP_LAUNCH_CHECK();
+    int rc = sort_pairs<KeyT>(keys, tl.ids + rg.p_lo, sorted, p.perm, rg.m_own, 0, 2 * bits, p.scratch, p.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_mo_inst1<KeyT><<<grid, kBlock, 0, st>>>(sorted, p.perm, p.ev, rg.m_own, inst, p.head);
+    PP_LAUNCH_CHECK();
+    rc = exclusive_scan<int32_t, int32_t>(p.head, rg.m_own, p.head_before, true, p.result, p.scratch, p.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_mo_types1<KeyT><<<grid, kBlock, 0, st>>>(sorted, bits, p.head_before, rg.m_own, rg.n_own, tptr, tlast, rowptr);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -1022,54 +1132,67 @@ using namespace pp;
 
 extern "C" {
 
-size_t pp_multiorder_prepare_ws_bytes(int64_t m) { return carve_mo_prep(nullptr, m).total_bytes; }
+size_t pp_multiorder_prepare_ws_bytes(int64_t m) { return carve_mo_prep(nullptr, m, m).total_bytes; }
 
+// `rg` == nullptr: level 1 of the whole stream.  Else of the events that start in the node range (list positions [p_lo, p_lo + m_own)):
+// inst / tptr / ibase / tlast / w / rowptr are the rank's own, numbered from 0; `tab` and `ev` stay whole-stream.
 static int mo_prepare(const int64_t* edge_index, int64_t m, int64_t num_nodes, const float* weight, const TemporalLists& tl, int64_t n_list,
                       bool sort_lists, void* tab, void* inst, int32_t* tptr, int32_t* ibase, int32_t* tlast, float* w, int32_t* rowptr, void* ws, size_t ws_bytes,
-                      hipStream_t st) {
+                      hipStream_t st, const MoRange* rg = nullptr) {
     PP_REQUIRE(m > 0 && num_nodes > 0, PP_ERR_ARG, "pp_multiorder_prepare: empty stream");
     PP_REQUIRE(m < (int64_t)0x7ffffff0 && num_nodes < ((int64_t)1 << 31), PP_ERR_TOO_LARGE, "pp_multiorder_prepare: m or num_nodes >= 2^31");
-    MoPrepWs p = carve_mo_prep(ws, m);
+    const int64_t mo = rg ? rg->m_own : m, nn = rg ? rg->n_own : num_nodes;       // the events / nodes level 1 is built from
+    const int32_t pbase = rg ? (int32_t)rg->p_lo : 0;
+    MoPrepWs p = carve_mo_prep(ws, mo, m);
     PP_REQUIRE(ws_bytes >= p.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_prepare: workspace too small");
     PP_HIP(hipMemsetAsync(p.result, 0, 4 * sizeof(int64_t), st));
     PP_HIP(hipMemsetAsync(p.counters, 0, 4 * sizeof(int32_t), st));
-    PP_HIP(hipMemsetAsync(p.csum, 0, (size_t)m * sizeof(int32_t), st));
+    PP_HIP(hipMemsetAsync(p.csum, 0, (size_t)mo * sizeof(int32_t), st));
     const int64_t* src = edge_index;
     const int64_t* dst = edge_index + m;
-    const unsigned grid = (unsigned)ceil_div(m, kBlock);
+    const unsigned grid = (unsigned)ceil_div(mo, kBlock);
     const int bits = bits_for((uint64_t)(num_nodes - 1));
     int rc;
     bool tab_done = false;               // (the list kernels write the window table on their way)
     if (sort_lists && tl.rowptr != nullptr) {
         // the per-node lists of pp_temporal_count, every list sorted by target in LDS: no second global sort
-        k_mo_events<<<grid, kBlock, 0, st>>>(dst, tl.first_pos, tl.count, weight, m, num_nodes, p.ev);
+        k_mo_events<<<(unsigned)ceil_div(m, kBlock), kBlock, 0, st>>>(dst, tl.first_pos, tl.count, weight, m, num_nodes, p.ev);
         PP_LAUNCH_CHECK();
-        const int64_t pieces = ceil_div(num_nodes, kBlock);
-        PP_HIP(hipMemsetAsync(p.head, 0, (size_t)m * sizeof(int32_t), st));       // (a list beyond the workgroup kernel stays unwritten: no heads there)
-        k_mo_lists_wave<<<(unsigned)(pieces < 4096 ? pieces : 4096), kBlock, 0, st>>>(num_nodes, tl.rowptr, tl.ids, p.ev, (uint4*)inst, p.head, (uint4*)tab,
-                                                                                      p.long_list, p.counters, p.result + 1);
+        const uint32_t* list_ptr = tl.rowptr + (rg ? rg->node_lo : 0);
+        uint4* tab_here = rg ? nullptr : (uint4*)tab;      // (a range: the other nodes' lists are nobody's here — k_mo_tab writes the whole table)
+        const int64_t pieces = ceil_div(nn, kBlock);
+        PP_HIP(hipMemsetAsync(p.head, 0, (size_t)mo * sizeof(int32_t), st));      // (a list beyond the workgroup kernel stays unwritten: no heads there)
+        k_mo_lists_wave<<<(unsigned)(pieces < 4096 ? pieces : 4096), kBlock, 0, st>>>(nn, list_ptr, tl.ids, p.ev, (uint4*)inst, p.head, tab_here,
+                                                                                      p.long_list, p.counters, p.result + 1, pbase);
         PP_LAUNCH_CHECK();
-        k_mo_lists_big<<<1024, kBlock, 0, st>>>(tl.rowptr, tl.ids, p.ev, (uint4*)inst, p.head, (uint4*)tab, p.long_list, p.counters);
-        tab_done = true;
+        k_mo_lists_big<<<1024, kBlock, 0, st>>>(list_ptr, tl.ids, p.ev, (uint4*)inst, p.head, tab_here, p.long_list, p.counters, pbase);
+        tab_done = rg == nullptr;
         PP_LAUNCH_CHECK();
-        rc = exclusive_scan<int32_t, int32_t>(p.head, m, p.head_before, true, p.result, p.scratch, p.scratch_bytes, st);
+        rc = exclusive_scan<int32_t, int32_t>(p.head, mo, p.head_before, true, p.result, p.scratch, p.scratch_bytes, st);
         if (rc != PP_OK) return rc;
-        const int64_t longest = m > num_nodes + 1 ? m : num_nodes + 1;
-        k_mo_types1_lists<<<(unsigned)ceil_div(longest, kBlock), kBlock, 0, st>>>((const uint4*)inst, p.head_before, tl.rowptr, m, num_nodes, tptr, tlast, rowptr);
+        const int64_t longest = mo > nn + 1 ? mo : nn + 1;
+        k_mo_types1_lists<<<(unsigned)ceil_div(longest, kBlock), kBlock, 0, st>>>((const uint4*)inst, p.head_before, list_ptr, mo, nn, tptr, tlast, rowptr,
+                                                                                  (uint32_t)pbase);
         PP_LAUNCH_CHECK();
         PP_HIP(hipMemsetAsync(p.counters, 0, 4 * sizeof(int32_t), st));          // (the list of long lists is done with; k_mo_sums1 fills its own)
+    } else if (rg) {
+        k_mo_events<<<(unsigned)ceil_div(m, kBlock), kBlock, 0, st>>>(dst, tl.first_pos, tl.count, weight, m, num_nodes, p.ev);
+        PP_LAUNCH_CHECK();
+        rc = 2 * bits <= 32 ? mo_level1_range<uint32_t>(p, tl, src, dst, *rg, num_nodes, bits, (uint4*)inst, tptr, tlast, rowptr, st)
+                            : mo_level1_range<uint64_t>(p, tl, src, dst, *rg, num_nodes, bits, (uint4*)inst, tptr, tlast, rowptr, st);
+        if (rc != PP_OK) return rc;
     } else {
         rc = 2 * bits <= 32 ? mo_level1<uint32_t>(p, tl, src, dst, weight, m, num_nodes, bits, (uint4*)inst, tptr, tlast, rowptr, st)
                             : mo_level1<uint64_t>(p, tl, src, dst, weight, m, num_nodes, bits, (uint4*)inst, tptr, tlast, rowptr, st);
         if (rc != PP_OK) return rc;
     }
-    if (weight) k_mo_sums1<true><<<grid, kBlock, 0, st>>>(tptr, p.head_before + m, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
-    else k_mo_sums1<false><<<grid, kBlock, 0, st>>>(tptr, p.head_before + m, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
+    if (weight) k_mo_sums1<true><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
+    else k_mo_sums1<false><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
     PP_LAUNCH_CHECK();
     if (weight) k_mo_sums1_long<true><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
     else k_mo_sums1_long<false><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
     PP_LAUNCH_CHECK();
-    rc = exclusive_scan<int32_t, int32_t>(p.csum, m, ibase, true, p.result + 2, p.scratch, p.scratch_bytes, st);
+    rc = exclusive_scan<int32_t, int32_t>(p.csum, mo, ibase, true, p.result + 2, p.scratch, p.scratch_bytes, st);
     if (rc != PP_OK) return rc;
     if (n_list > 0 && !tab_done) k_mo_tab<<<(unsigned)ceil_div(n_list, kBlock), kBlock, 0, st>>>(tl.ids, p.ev, n_list, (uint4*)tab);
     PP_LAUNCH_CHECK();
@@ -1085,6 +1208,67 @@ int pp_multiorder_prepare(const int64_t* edge_index, int64_t m, int64_t num_node
     const TemporalLists tl = temporal_lists(lift_ws, m, num_nodes);
     PP_REQUIRE(lift_ws_bytes >= tl.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_prepare: not a pp_temporal_count workspace of this stream");
     return mo_prepare(edge_index, m, num_nodes, weight, tl, m, radix_sort == 0, tab, inst, tptr, ibase, tlast, w, rowptr, ws, ws_bytes, (hipStream_t)stream);
+}
+
+/* see include/pathpyg_amd.h: per-node loads of the split by first node */
+size_t pp_multiorder_node_loads_ws_bytes(int64_t m) { return carve_mo_loads(nullptr, m).total_bytes; }
+
+int pp_multiorder_node_loads(int64_t m, int64_t num_nodes, void* lift_ws, size_t lift_ws_bytes, int64_t* loads, void* ws, size_t ws_bytes,
+                             pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(m > 0 && num_nodes > 0, PP_ERR_ARG, "pp_multiorder_node_loads: empty stream");
+    PP_REQUIRE(m < (int64_t)0x7ffffff0 && num_nodes < ((int64_t)1 << 31), PP_ERR_TOO_LARGE, "pp_multiorder_node_loads: m or num_nodes >= 2^31");
+    const TemporalLists tl = temporal_lists(lift_ws, m, num_nodes);
+    PP_REQUIRE(lift_ws_bytes >= tl.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_node_loads: not a pp_temporal_windows workspace of this stream");
+    MoLoadsWs p = carve_mo_loads(ws, m);
+    PP_REQUIRE(ws_bytes >= p.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_node_loads: workspace too small");
+    k_mo_list_counts<<<(unsigned)ceil_div(m, kBlock), kBlock, 0, st>>>(tl.ids, tl.count, m, p.counts);
+    PP_LAUNCH_CHECK();
+    const int rc = exclusive_scan<int32_t, int64_t>(p.counts, m, p.prefix, true, p.total, p.scratch, p.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_mo_node_loads<<<(unsigned)ceil_div(num_nodes + 1, kBlock), kBlock, 0, st>>>(tl.rowptr, p.prefix, num_nodes, loads);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+/* see include/pathpyg_amd.h: level 1 of the events that start in a node range */
+size_t pp_multiorder_prepare_range_ws_bytes(int64_t m, int64_t m_own) { return carve_mo_prep(nullptr, m_own, m).total_bytes; }
+
+int pp_multiorder_prepare_range(const int64_t* edge_index, int64_t m, int64_t num_nodes, const float* weight, void* lift_ws, size_t lift_ws_bytes,
+                                int64_t node_lo, int64_t node_hi, int64_t p_lo, int64_t m_own, int radix_sort, void* tab, void* inst, int32_t* tptr,
+                                int32_t* ibase, int32_t* tlast, float* w, int32_t* rowptr, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    PP_REQUIRE(m > 0 && num_nodes > 0, PP_ERR_ARG, "pp_multiorder_prepare_range: empty stream");
+    PP_REQUIRE(node_lo >= 0 && node_lo < node_hi && node_hi <= num_nodes, PP_ERR_ARG, "pp_multiorder_prepare_range: node range [%lld, %lld) outside [0, %lld]",
+               (long long)node_lo, (long long)node_hi, (long long)num_nodes);
+    PP_REQUIRE(p_lo >= 0 && m_own > 0 && p_lo + m_own <= m, PP_ERR_ARG, "pp_multiorder_prepare_range: list range [%lld, %lld) outside [0, %lld] or empty",
+               (long long)p_lo, (long long)(p_lo + m_own), (long long)m);
+    const TemporalLists tl = temporal_lists(lift_ws, m, num_nodes);
+    PP_REQUIRE(lift_ws_bytes >= tl.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_prepare_range: not a pp_temporal_windows workspace of this stream");
+    const MoRange rg{node_lo, node_hi - node_lo, p_lo, m_own};
+    return mo_prepare(edge_index, m, num_nodes, weight, tl, m, radix_sort == 0, tab, inst, tptr, ibase, tlast, w, rowptr, ws, ws_bytes, (hipStream_t)stream, &rg);
+}
+
+/* see include/pathpyg_amd.h: cand_ptr / cand_last of the next step from the all-gathered per-rank pieces */
+int pp_multiorder_stitch(const int32_t* gathered, int64_t stride, int64_t last_at, int world, const int64_t* row_lo, const int64_t* edge_lo,
+                         int32_t* cand_ptr, int32_t* cand_last, pp_stream_t stream) {
+    PP_REQUIRE(world >= 1 && world <= kMoMaxWorld, PP_ERR_ARG, "pp_multiorder_stitch: 1 .. %d ranks", kMoMaxWorld);
+    PP_REQUIRE(stride >= 0 && last_at >= 0 && last_at <= stride, PP_ERR_ARG, "pp_multiorder_stitch: bad block layout");
+    MoStitch sa;
+    sa.world = world;
+    PP_REQUIRE(row_lo[0] == 0 && edge_lo[0] == 0, PP_ERR_ARG, "pp_multiorder_stitch: the ranges start at 0");
+    for (int r = 0; r <= world; ++r) {
+        PP_REQUIRE(row_lo[r] >= 0 && edge_lo[r] >= 0 && row_lo[r] < (int64_t)0x7ffffff0 && edge_lo[r] < (int64_t)0x7ffffff0, PP_ERR_TOO_LARGE,
+                   "pp_multiorder_stitch: 2^31 or more rows or edges");
+        if (r < world)         // every rank's piece lies inside its block
+            PP_REQUIRE(row_lo[r + 1] >= row_lo[r] && row_lo[r + 1] - row_lo[r] <= last_at && edge_lo[r + 1] >= edge_lo[r] &&
+                           edge_lo[r + 1] - edge_lo[r] <= stride - last_at, PP_ERR_ARG, "pp_multiorder_stitch: rank %d's piece does not fit its block", r);
+        sa.row_lo[r] = (int32_t)row_lo[r];
+        sa.edge_lo[r] = (int32_t)edge_lo[r];
+    }
+    const int64_t total = row_lo[world] + 1 + edge_lo[world];
+    k_mo_stitch<<<(unsigned)ceil_div(total, kBlock), kBlock, 0, (hipStream_t)stream>>>(gathered, stride, last_at, sa, cand_ptr, cand_last);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
 }
 
 size_t pp_multiorder_graph_ws_bytes(int64_t m, int64_t num_event_edges) { return carve_mo_graph(nullptr, m, num_event_edges).total_bytes; }

@@ -1,4 +1,4 @@
-"""Multi-GPU sharding: one process per GPU, ``torch.distributed`` (backend ``nccl`` = RCCL on ROCm).  Three parts:
+"""Multi-GPU sharding: one process per GPU, ``torch.distributed`` (backend ``nccl`` = RCCL on ROCm).  Four parts:
 
 * transport — :class:`Comm`: the collectives, byte counters and a per-collective log; host-staged for gloo (tests), and R ranks as
   threads of one process on one GPU (:class:`ThreadWorld`, :func:`run_thread_world`).  Every collective of this module goes through it;
@@ -6,7 +6,8 @@
   :func:`lift_order_edge_index_sharded`), key-range sharded aggregation (:func:`coalesce_sharded`, :func:`unique_pairs_sharded`,
   :func:`second_order_layer_sharded`), :func:`all_reduce_gradients`.  Device work goes through ``ops`` (default: ``_dispatch``);
 * the partitioned DBGNN builders — :func:`build_dbgnn_shard` (node-range split on the node-by-node order-2 builder, else the edge-range
-  split of :func:`_build_partitioned`), graph shards with their halo exchanges, :class:`~pathpyg_amd.nn.sharded.ShardedDBGNN`.
+  split of :func:`_build_partitioned`), graph shards with their halo exchanges, :class:`~pathpyg_amd.nn.sharded.ShardedDBGNN`;
+* the De Bruijn layers of ALL orders split by first node — :func:`build_multi_order_shard`, :func:`gather_multi_order`, :func:`multi_order_cuts`.
 """
 from __future__ import annotations
 
@@ -1427,3 +1428,189 @@ def second_order_layer_sharded(g, delta=1, group=None, edge_weight: torch.Tensor
     edges, weights, cuts = coalesce_sharded(u, v, w[i], num_ho, comm=comm, ops=ops)
     return {"edge_index": edges, "edge_weight": weights, "node_sequence": pairs, "num_nodes": num_ho, "row_cuts": cuts,
             "instance_pairs_total": total, "own_event_ids": own_ids}
+
+
+# =====================================================================================================
+# All De Bruijn layers 1..K on N ranks, split by FIRST NODE (level-by-level builder, csrc/pp_multiorder.hip).  Types are kept in lexicographic
+# order of their node sequences and a child of type s has type s ++ d: the rank that owns the first-order nodes [lo, hi) as first nodes owns
+# a contiguous block of types at every level = a contiguous block of rows of every layer >= 2, with all their out-edges.  The whole
+# recursion stays on the rank; the only thing it reads from elsewhere is the column lookup suffix(s) ++ d against the finished layer's
+# {row_ptr, last}: one all-gather per level.
+# =====================================================================================================
+class MultiOrderShardLayer:
+    """A rank's rows of layer k (:func:`build_multi_order_shard`): ``n_nodes`` / ``n_edges`` global; the owned rows are ``[row_lo, row_hi)``
+    (global ids), the owned edges start at the global id ``edge_lo``; ``n_instances``: the order-k instances the rank lifted; ``row_ptr``
+    int32 [row_hi - row_lo + 1] holds offsets into the rank's OWN edges, ``col`` int32 GLOBAL columns, ``weight`` float32, ``last`` int32
+    last first-order node of every edge (``None`` for the top layer).  ``row_cuts`` / ``edge_cuts`` [world + 1]: every rank's first row /
+    edge, ``instances``: the instances of all ranks."""
+
+    __slots__ = ("n_nodes", "n_edges", "row_lo", "row_hi", "edge_lo", "n_instances", "row_ptr", "col", "weight", "last", "row_cuts", "edge_cuts",
+                 "instances")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class MultiOrderShard:
+    """Result of :func:`build_multi_order_shard`: ``layers[k - 1]`` = this rank's :class:`MultiOrderShardLayer` of layer k; ``cuts`` [world + 1]
+    the first-node cuts; ``delta`` / ``weight``: what the build was asked for (:func:`gather_multi_order` hands them on)."""
+
+    __slots__ = ("rank", "world", "cuts", "layers", "delta", "weight")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def multi_order_cuts(loads_prefix: torch.Tensor, world: int) -> list[int]:
+    """First-node cuts ``[world + 1]`` balanced on the level-2 instance loads: ``loads_prefix`` int64 [n + 1] (any device) holds the load of
+    the nodes below v; cut r is the first node whose prefix reaches ``r * total / world``, cut 0 is 0 and cut ``world`` is n.  A rank's load is
+    then below ``total / world`` + the largest single-node load.  Exact integer arithmetic on a replicated input: every rank derives the same
+    cuts, no collective; two read-backs of O(world) values."""
+    n = int(loads_prefix.numel()) - 1
+    if world < 1 or n < 0:
+        raise ValueError("multi_order_cuts: world >= 1 and a prefix of at least one entry")
+    total = int(loads_prefix[-1])
+    targets = torch.tensor([-((-r * total) // world) for r in range(world + 1)], dtype=torch.int64, device=loads_prefix.device)
+    cuts = torch.searchsorted(loads_prefix.contiguous(), targets, right=False).clamp_(max=n).tolist()
+    cuts[0], cuts[world] = 0, n
+    return [int(c) for c in cuts]
+
+
+def _prefix(counts) -> list[int]:
+    out = [0]
+    for c in counts:
+        out.append(out[-1] + int(c))
+    return out
+
+
+def _gather_pieces(comm: Comm, ops, row_ptr_local: torch.Tensor, edge_arrays: list, row_cuts: list[int], edge_cuts: list[int]):
+    """ONE all-gather of every rank's ``{row_ptr (without its last entry), edge arrays}`` (int32, padded to the largest rank), then one stitch
+    launch per edge array: ``(row_ptr_global [rows + 1], [edge array global, ...])``."""
+    world, rank = comm.world, comm.rank
+    cap_rows = max(row_cuts[r + 1] - row_cuts[r] for r in range(world))
+    cap_edges = max(edge_cuts[r + 1] - edge_cuts[r] for r in range(world))
+    n_rows, n_edges = row_cuts[rank + 1] - row_cuts[rank], edge_cuts[rank + 1] - edge_cuts[rank]
+    stride = cap_rows + len(edge_arrays) * cap_edges
+    block = torch.empty(max(stride, 1), dtype=torch.int32, device=row_ptr_local.device)
+    block[:n_rows] = row_ptr_local[:n_rows]
+    for j, a in enumerate(edge_arrays):
+        at = cap_rows + j * cap_edges
+        block[at: at + n_edges] = a[:n_edges].view(torch.int32)
+    gathered = comm.all_gather_rows(block)
+    row_ptr_global, out = None, []
+    for j in range(len(edge_arrays)):
+        row_ptr_global, e = ops.multi_order_stitch(gathered, block.numel(), cap_rows + j * cap_edges, row_cuts, edge_cuts)
+        out.append(e)
+    return row_ptr_global, out
+
+
+def build_multi_order_shard(g, delta, max_order: int, comm: Comm, ops=None, weight: str = "edge_weight") -> "MultiOrderShard | None":
+    """This rank's rows of ALL De Bruijn layers 1..``max_order`` of a time-sorted stream replicated on every rank — what
+    ``MultiOrderModel.from_temporal_graph(g, delta, max_order >= 3)`` builds on one GPU (reference multi_order_model.py:124-192, 83-122), split by
+    first node.  Per rank: the windows pass on the whole stream and the per-node loads (``ops.multi_order_node_loads``), the cuts
+    (:func:`multi_order_cuts`, no collective), level 1 on the own node range (``ops.multi_order_prepare_range``); then per order one step on the
+    own types (``ops.multi_order_step``, skipped by a rank that owns none), one all-gather of ``{types, children, status}`` and — except after
+    the top layer — one all-gather of the finished layer's ``{row_ptr, last}`` (4 B per node + 4 B per edge), stitched into the global
+    candidate tables by one launch (``ops.multi_order_stitch``).  Instance buffers are per rank: the 2^31-instance limit applies to a rank's
+    share, layer edge ids stay int32 (below 2^31 globally).
+
+    ``None`` on EVERY rank at the same level (collective decisions, nobody is left in a collective): a type with more than 4096 children on
+    some rank, a layer without edges, a level with 2^31 or more edges globally or children on one rank.  ``None`` without any collective (the
+    inputs are replicated, so all ranks decide alike): an empty stream, one that is not sorted by time, a weight that is not float32 and what
+    ``ops`` refuses (``HipOps``: tensors on the host).  The caller then runs the generic kernels on one rank, as ``from_temporal_graph`` does."""
+    ops = _ops_default(ops)
+    max_order = int(max_order)
+    if max_order < 1:
+        raise ValueError("build_multi_order_shard: max_order >= 1")
+    data = g.data
+    ei, time = _dispatch.plain(data.edge_index), data.time
+    if ei is None or time is None:
+        return None
+    n, m = int(data.num_nodes), int(ei.size(1))
+    w = data[weight] if weight in data else None
+    if n == 0 or m == 0 or (w is not None and (not isinstance(w, torch.Tensor) or w.dtype != torch.float32)):
+        return None
+    started = ops.multi_order_node_loads(ei, time, n, delta, w)
+    if started is None:
+        return None
+    windows, loads = started
+    dev = loads.device
+    world, rank = comm.world, comm.rank
+    cuts = multi_order_cuts(loads[1], world)
+    lo, hi = cuts[rank], cuts[rank + 1]
+    p_lo, p_hi = (int(v) for v in loads[0][[lo, hi]].tolist())
+    comm.mark("mo windows")
+    i32 = dict(dtype=torch.int32, device=dev)
+
+    def nothing(rows: int, top: bool):
+        # the level of a rank that owns no type: empty slices in every gather, no launch
+        return _hip.MultiOrderLevel(types=0, children=0, status=0, row_ptr=torch.zeros(rows + 1, **i32), col=torch.empty(0, **i32),
+                                    weight=torch.empty(0, dtype=torch.float32, device=dev), tlast=None if top else torch.empty(0, **i32))
+
+    tab = None
+    if p_hi > p_lo:
+        level_local, tab = ops.multi_order_prepare_range(windows, lo, hi, p_lo, p_hi - p_lo)
+    else:
+        level_local = nothing(hi - lo, max_order == 1)
+    del windows
+    row_cuts_global, own_instances = list(cuts), p_hi - p_lo
+    instances_global = m
+    layers = []
+    for k in range(1, max_order + 1):
+        top = k == max_order
+        # {new types, new children, status}: the global edge offsets and the agreement on fallbacks
+        info = comm.all_gather_ints([level_local.types, level_local.children, level_local.status], dev)
+        status = 0
+        for row in info:
+            status |= row[2]
+        _hip._bad_index(status, "build_multi_order_shard")
+        edge_cuts_global = _prefix(row[0] for row in info)
+        n_edges = edge_cuts_global[-1]
+        if status & (2 | 4) or n_edges == 0 or n_edges >= _hip._INT32_ROWS:
+            return None
+        types_local = level_local.types
+        layers.append(MultiOrderShardLayer(
+            n_nodes=row_cuts_global[-1], n_edges=n_edges, row_lo=row_cuts_global[rank], row_hi=row_cuts_global[rank + 1], edge_lo=edge_cuts_global[rank],
+            n_instances=own_instances, row_ptr=level_local.row_ptr, col=level_local.col[:types_local], weight=level_local.weight[:types_local],
+            last=None if top else level_local.tlast[:types_local], row_cuts=row_cuts_global, edge_cuts=edge_cuts_global, instances=instances_global))
+        comm.mark(f"mo level {k}")
+        if top:
+            break
+        children = [row[1] for row in info]
+        if sum(children) == 0 or max(children) >= _hip._INT32_ROWS:
+            return None
+        # the finished layer's {row_ptr, last} of every rank -> the GLOBAL tables the next step looks its columns up in
+        cand_ptr_global, (cand_last_global,) = _gather_pieces(comm, ops, level_local.row_ptr, [level_local.tlast], row_cuts_global, edge_cuts_global)
+        if level_local.types > 0 and level_local.children > 0:
+            nxt = ops.multi_order_step(level_local, cand_ptr_global, cand_last_global, tab, w is not None, k + 1 == max_order)
+        else:
+            nxt = nothing(level_local.types, k + 1 == max_order)
+        own_instances, instances_global = level_local.children, sum(children)
+        row_cuts_global = edge_cuts_global
+        level_local = nxt
+        del cand_ptr_global, cand_last_global
+    return MultiOrderShard(rank=rank, world=world, cuts=cuts, layers=layers, delta=delta, weight=weight)
+
+
+def gather_multi_order(shard: MultiOrderShard, comm: Comm, g, cached: bool = True, ops=None):
+    """The :class:`~pathpyg_amd.core.multi_order_model.MultiOrderModel` that ``from_temporal_graph(g, delta, max_order)`` returns on one GPU, on
+    every rank, from the ranks' shards: per layer one all-gather of ``{row_ptr, col, weight, last}``; the layer tensors are the same deferred
+    views (``_csr_layers``), ``sizes["layers"]`` the same, ``inverse_idx`` of the layers from 3 on comes from the generic kernels on first use.
+    The convenience and test path — not something a training loop calls per step.  ``ops``: as for the build (its ``multi_order_stitch``
+    places the pieces; a stand-in without a GPU also supplies ``gather_concat`` for the node sequences)."""
+    from .core import multi_order_model as mm
+    ops = _ops_default(ops)
+    built = []
+    for k, layer in enumerate(shard.layers, start=1):
+        arrays = [layer.col, layer.weight] + ([] if layer.last is None else [layer.last])
+        row_ptr, gathered = _gather_pieces(comm, ops, layer.row_ptr, arrays, layer.row_cuts, layer.edge_cuts)
+        built.append(_hip.MultiOrderLayer(n_nodes=layer.n_nodes, n_edges=layer.n_edges, n_instances=layer.instances, row_ptr=row_ptr, col=gathered[0],
+                                          weight=gathered[1].view(torch.float32), last=None if layer.last is None else gathered[2]))
+    ei = _dispatch.plain(g.data.edge_index)
+    out = mm.MultiOrderModel()
+    out.sizes = {"m": int(ei.size(1)), "N": int(g.data.num_nodes), "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in built]}
+    out.layers = mm._csr_layers(g, ei, built, cached, inverse_high=mm._generic_inverses(g, shard.delta, len(built), shard.weight, cached, None),
+                                gather_concat=getattr(ops, "gather_concat", None))
+    return out

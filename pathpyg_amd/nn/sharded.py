@@ -55,6 +55,12 @@ class HipOps:
     ptr_from_sorted = staticmethod(_hip.ptr_from_sorted)
     degree = staticmethod(_hip.degree)
 
+    # ---- all De Bruijn layers split by first node (distributed.build_multi_order_shard)
+    multi_order_node_loads = staticmethod(_hip.multi_order_node_loads)
+    multi_order_prepare_range = staticmethod(_hip.multi_order_prepare_range)
+    multi_order_step = staticmethod(_hip.multi_order_step)
+    multi_order_stitch = staticmethod(_hip.multi_order_stitch)
+
     @staticmethod
     def group_rows(keys: torch.Tensor, num_rows: int):
         """(ptr int32 [num_rows+1], order int32 [n]): stable grouping of positions by ``keys`` (values in [0, num_rows))."""
