@@ -556,6 +556,19 @@ int pp_gcn_input_grad_drop_f32(const int32_t* ptr, const int32_t* idx, const flo
                                const float* self_coef, const float* W, int K, const float* X_act, int fuse_act, const int32_t* heavy_slot,
                                const float* heavy_sum, float* d_in, float* colsum_in, void* ws, size_t ws_bytes, double drop_p, int64_t drop_seed,
                                int64_t drop_tag, int64_t drop_row0, pp_stream_t stream);
+/* pp_gcn_backward_nnz_f32 of the SECOND layer of a stack whose first layer's input takes no gradient (the stacks of reference
+ * src/pathpyG/nn/dbgnn.py:131-140: x and x_h are data): d_in, the gradient w.r.t. the first layer's pre-activation, is consumed where it is
+ * formed —  dW_below[K,K_below] = d_in^T agg_below  with agg_below [n_rows,K_below] the agg_out of the first layer's forward call — and never
+ * stored (d_in is ignored and may be NULL).  Replaces pp_gcn_backward_nnz_f32 + pp_weight_grad_f32: one write and one read of an
+ * n_rows x 64 matrix and one launch less.  colsum_in and dW as above.  One variant only; PP_ERR_ARG unless M == K == K_below == 64,
+ * fuse_act, colsum_in != NULL, n_self == n_rows, heavy_slot == NULL, drop_p == 0 and the matrices fit 32-bit byte offsets.
+ * ws: pp_gcn_backward_below_ws_bytes(n_rows) (two sets of partial tiles). */
+size_t pp_gcn_backward_below_ws_bytes(int64_t n_rows);
+int pp_gcn_backward_below_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, int64_t n_self, int64_t nnz, const float* D, int M,
+                              const float* self_coef, const float* X, int K, const float* W, int fuse_act, const int32_t* heavy_slot,
+                              const float* heavy_sum, float* d_in, float* colsum_in, float* dW, void* ws, size_t ws_bytes, double drop_p,
+                              int64_t drop_seed, int64_t drop_tag, int64_t drop_row0, const float* agg_below, int K_below, float* dW_below,
+                              pp_stream_t stream);
 
                           /* ws: pp_wide_layer_ws_bytes(M, K) for the shapes served by pp_wide_layer_f32 (a side of 256), else unused */
 

@@ -1506,6 +1506,29 @@ def gcn_backward(ptr, idx, val, n_rows: int, dpre: torch.Tensor, self_coef, x: t
     return d_in, colsum, dw
 
 
+def gcn_backward_below(ptr, idx, val, n_rows: int, dpre: torch.Tensor, self_coef, x: torch.Tensor, weight: torch.Tensor, agg_below: torch.Tensor):
+    """:func:`gcn_backward` of the second layer of a stack whose first layer takes no input gradient, with that layer's weight gradient
+    formed in the same kernel: ``(colsum, dW, dW_below)`` where ``colsum`` = column sums of ``d_in = (G W) * ELU'(x)`` (the first layer's bias
+    gradient) and ``dW_below = d_in^T agg_below`` (``agg_below`` = the ``A x`` kept by the first layer's :func:`gcn_forward`).  ``d_in`` is never
+    stored.  64-wide layers on a whole graph without hub rows and without dropout only: anything else is a ValueError."""
+    dev = require_device(ptr, idx, val, dpre, self_coef, x, weight, agg_below)
+    dpre, x, weight, agg_below = dpre.contiguous(), x.contiguous(), weight.contiguous(), agg_below.contiguous()
+    m, k = weight.shape
+    if dpre.size(1) != m or x.size(1) != k or x.size(0) != n_rows or dpre.size(0) < n_rows or agg_below.size(0) != n_rows:
+        raise ValueError("gcn_backward_below: shapes do not match")
+    L = lib()
+    with torch.cuda.device(dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        colsum = torch.empty(k, **f32)
+        dw = torch.empty((m, k), **f32)
+        dw_below = torch.empty((k, agg_below.size(1)), **f32)
+        ws = _workspace(L.pp_gcn_backward_below_ws_bytes(n_rows), dev)
+        check(L.pp_gcn_backward_below_f32(_p(ptr), _p(idx), _p(val), n_rows, n_rows, int(idx.numel()), _p(dpre), m, _p(self_coef), _p(x), k, _p(weight),
+                                          1, None, None, None, _p(colsum), _p(dw), _p(ws), ws.numel(), 0.0, 0, 0, 0, _p(agg_below),
+                                          agg_below.size(1), _p(dw_below), _stream()), "pp_gcn_backward_below_f32")
+    return colsum, dw, dw_below
+
+
 def gcn_fused_supported(p: int, q: int) -> int:
     """1: fused forward + one-kernel backward (widths 16/32/64); 2: fused forward + input-gradient kernel (128-wide shapes); 0: neither."""
     return int(lib().pp_gcn_fused_supported(int(p), int(q)))

@@ -602,12 +602,62 @@ __device__ __forceinline__ void buf_store_f4(buf_t r, uint32_t off, float4 v) {
 #ifndef PP_BWD_BATCH
 #define PP_BWD_BATCH 0
 #endif
-template <int M, int K, bool kHeavy, bool kWide, bool kDrop = false, bool kCap = false>
-__global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_WAVES : 1) void k_gcn_backward(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
+// kBelow (64 x 64, short rows, the layer below takes no input gradient): the kernel also forms that layer's weight gradient
+// dW_below = d_in^T AGG from the d_in tile it holds in registers (AGG = the A_hat x the forward kernel kept) and does not store d_in:
+// the write and the re-read of d_in and the k_weight_grad64 launch go away.  64 more accumulator registers: 2 waves per SIMD.
+// PP_BELOW_AGG_AT: where the AGG rows are fetched — 0 before the gather, 1 after it (with the late X rows), 2 after the dW MFMAs.
+// Measured at 10^7 rows (one process, medians of 3 x 10 launches; gcn_backward + weight_grad with the d_in allocation: 3.46-3.61 ms):
+// AGG_AT 0: 3.16-3.18 ms (13 spilled registers), 1: 3.06-3.08 (6 spilled; kept), 2: 3.08; nt loads of AGG: 3.05-3.06 at AGG_AT 1, 3.07-3.09
+// at 2 (inside the run-to-run spread: left off); X rows before the gather (PP_BELOW_LATE_X 0, 13 spilled): 3.07-3.10, no gain at 2 waves.
+#ifndef PP_BELOW_AGG_AT
+#define PP_BELOW_AGG_AT 1
+#endif
+#ifndef PP_BELOW_LATE_X
+#define PP_BELOW_LATE_X PP_BWD_LATE_X
+#endif
+#ifndef PP_BELOW_NT_AGG
+#define PP_BELOW_NT_AGG 0
+#endif
+__device__ __forceinline__ float4 buf_load_f4_nt(buf_t r, uint32_t off) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 2);               // aux bit 1 = nt (AGG is read exactly once)
+    float4 out;
+    __builtin_memcpy(&out, &v, 16);
+    return out;
+}
+#define PP_LOAD_AGG \
+        _Pragma("unroll") \
+        for (int reg = 0; reg < 4; ++reg) { \
+            const int64_t r = t * 16 + 4 * kq + reg; \
+            const uint32_t off = r < n_rows ? (uint32_t)r * (uint32_t)(K * 4) + 16u * i : kBufOob; \
+            const float4 v = PP_BELOW_NT_AGG ? buf_load_f4_nt(rs_agg, off) : buf_load_f4(rs_agg, off); \
+            ag[0][reg] = v.x; ag[1][reg] = v.y; ag[2][reg] = v.z; ag[3][reg] = v.w; \
+        }
+
+// the waves' [64][64] accumulator tiles summed through LDS in wave order: one partial tile per workgroup (zero padded) at dst
+template <int MT, int CT>
+__device__ __forceinline__ void fold_weight_tile(float* s_fold, const f32x4 (&acc)[MT][CT], int wave, int i, int kq, float* __restrict__ dst) {
+    for (int w = 0; w < kGcnWaves; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+                    for (int reg = 0; reg < 4; ++reg) s_fold[(MT * (4 * kq + reg) + mt) * 64 + CT * i + ct] += acc[mt][ct][reg];
+        }
+        __syncthreads();
+    }
+    for (int e = threadIdx.x; e < 64 * 64; e += kGcnThreads) dst[e] = s_fold[e];
+}
+template <int M, int K, bool kHeavy, bool kWide, bool kDrop = false, bool kCap = false, bool kBelow = false>
+__global__ __launch_bounds__(kGcnThreads, kBelow ? 2 : ((M == 64 && K == 64 && kCap) ? PP_BWD_WAVES : 1)) void k_gcn_backward(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                                                              const float* __restrict__ val, int64_t n_rows, const float* __restrict__ D,
                                                              const float* __restrict__ self_coef, const float* __restrict__ X,
                                                              const float* __restrict__ W, int fuse_act, HeavyRows heavy, float* __restrict__ d_in,
-                                                             float* __restrict__ colsum_in, float* __restrict__ partial_w, int64_t n_self, DropSite drop) {
+                                                             float* __restrict__ colsum_in, float* __restrict__ partial_w, int64_t n_self, DropSite drop,
+                                                             const float* __restrict__ AGG, float* __restrict__ partial_w_below) {
+    static_assert(!kBelow || (M == 64 && K == 64 && kCap && !kHeavy && !kWide && !kDrop), "kBelow: the 64 x 64 short-row variant only");
+    constexpr bool kLateX = kCap && (kBelow ? PP_BELOW_LATE_X : PP_BWD_LATE_X);
     constexpr int kLanes = M / 4, kGroups = kWave / kLanes, kRows = 16 / kGroups, KQ = M / 4, MT = M / 16, CT = K / 16, TS = M + 4;
     constexpr int kBatch = kRows < 2 ? kRows : 2;
     using off_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;     // byte offset of a gathered row
@@ -622,12 +672,19 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
     const int i = lane & 15, kq = lane >> 4;
     float* tile = s_tile[wave];
     const char* db = (const char*)D;
-    [[maybe_unused]] const buf_t rs_xin = buf_of(X), rs_din = buf_of(d_in);
+    [[maybe_unused]] const buf_t rs_xin = buf_of(X), rs_din = buf_of(d_in), rs_agg = buf_of(AGG);
     f32x4 acc_w[MT][CT];
+    [[maybe_unused]] f32x4 acc_below[kBelow ? CT : 1][kBelow ? CT : 1];          // dW_below[CT*row + mt][CT*col + ct], laid out as acc_w
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc_w[mt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (kBelow) {
+#pragma unroll
+        for (int mt = 0; mt < CT; ++mt)
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) acc_below[mt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     float col_in[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) col_in[ct] = 0.f;
@@ -639,7 +696,9 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
     if constexpr (!kWide) gather.prefetch((int64_t)blockIdx.x * kGcnWaves + wave);
     for (int64_t t = (int64_t)blockIdx.x * kGcnWaves + wave; t < n_tiles; t += step) {
         float xr[CT][4];
-        if constexpr (!(kCap && PP_BWD_LATE_X)) { PP_LOAD_XR }        // (in flight during the gather)
+        [[maybe_unused]] float ag[CT][4];                             // kBelow: AGG rows in the layout of xr (B operand of the dW_below stream)
+        if constexpr (!kLateX) { PP_LOAD_XR }                         // (in flight during the gather)
+        if constexpr (kBelow && PP_BELOW_AGG_AT == 0) { PP_LOAD_AGG }
         if constexpr (kWide) {
             const int64_t r0 = t * 16 + g * kRows;
             int p[kRows + 1];
@@ -729,7 +788,8 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
         } else {
             gather.run(t, t + step, tile, nullptr);
         }
-        if constexpr (kCap && PP_BWD_LATE_X) { PP_LOAD_XR }         // (capped variant: fetched AFTER the gather, 16 registers less while its loads are in flight)
+        if constexpr (kLateX) { PP_LOAD_XR }                        // (capped variant: fetched AFTER the gather, 16 registers less while its loads are in flight)
+        if constexpr (kBelow && PP_BELOW_AGG_AT == 1) { PP_LOAD_AGG }
         __builtin_amdgcn_wave_barrier();
         // ---------------------------------------------------------------- G . W  ->  d_in tile
         float4 a[KQ / 4];
@@ -773,6 +833,8 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
                 for (int ct = 0; ct < CT; ++ct)
                     acc_w[mt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(hr[mt][reg], xr[ct][reg], acc_w[mt][ct], 0, 0, 0);
         __builtin_amdgcn_wave_barrier();
+        if constexpr (kBelow && PP_BELOW_AGG_AT == 2) { PP_LOAD_AGG }
+        [[maybe_unused]] float vb[CT][4];                             // kBelow: the d_in tile, rows 4*kq + reg, columns CT*i + ct = A operand layout
         [[maybe_unused]] float* yp = d_in + (t * 16 + 4 * kq) * K + CT * i;
         const int rows_here = n_rows - (t * 16 + 4 * kq) < 4 ? (int)(n_rows - (t * 16 + 4 * kq)) : 4;
 #pragma unroll
@@ -791,8 +853,10 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
                     v[ct] *= y > 0.f ? 1.f : y + 1.f;
                 }
                 col_in[ct] += v[ct];                                  // rows past the end aggregate nothing: v == 0 there
+                if constexpr (kBelow) vb[ct][reg] = v[ct];
             }
-            if constexpr (CT == 4 && !kWide) {
+            if constexpr (kBelow) {                                   // d_in stays in registers: nothing else reads it
+            } else if constexpr (CT == 4 && !kWide) {
                 const uint32_t off = reg < rows_here ? (uint32_t)(t * 16 + 4 * kq + reg) * (uint32_t)(K * 4) + 16u * i : kBufOob;
                 if (stream_out) buf_store_f4_nt(rs_din, off, make_float4(v[0], v[1], v[2], v[3]));
                 else buf_store_f4(rs_din, off, make_float4(v[0], v[1], v[2], v[3]));
@@ -801,6 +865,16 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
                 else if constexpr (CT == 2) *(float2*)(yp + reg * K) = make_float2(v[0], v[1]);
                 else yp[reg * K] = v[0];
             }
+        }
+        if constexpr (kBelow) {
+            // ------------------------------------------------------------ dW_below += d_in_tile^T AGG_tile, the dW stream once more
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg)
+#pragma unroll
+                for (int mt = 0; mt < CT; ++mt)
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct)
+                        acc_below[mt][ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(vb[mt][reg], ag[ct][reg], acc_below[mt][ct], 0, 0, 0);
         }
     }
     if (colsum_in) {
@@ -813,19 +887,13 @@ __global__ __launch_bounds__(kGcnThreads, (M == 64 && K == 64 && kCap) ? PP_BWD_
         }
     }
     // fold the waves' dW through LDS in wave order: one partial [64][64] tile per workgroup (zero padded), summed by weight_grad_reduce
-    for (int w = 0; w < kGcnWaves; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                    for (int reg = 0; reg < 4; ++reg) s_fold[(MT * (4 * kq + reg) + mt) * 64 + CT * i + ct] += acc_w[mt][ct][reg];
-        }
+    fold_weight_tile<MT, CT>(s_fold, acc_w, wave, i, kq, partial_w + ((int64_t)blockIdx.x << 12));
+    if constexpr (kBelow) {
         __syncthreads();
+        for (int e = threadIdx.x; e < 64 * 64; e += kGcnThreads) s_fold[e] = 0.f;
+        __syncthreads();
+        fold_weight_tile<CT, CT>(s_fold, acc_below, wave, i, kq, partial_w_below + ((int64_t)blockIdx.x << 12));
     }
-    float* pw = partial_w + ((int64_t)blockIdx.x << 12);
-    for (int e = threadIdx.x; e < 64 * 64; e += kGcnThreads) pw[e] = s_fold[e];
 }
 
 constexpr int64_t kGcnBackwardMaxBlocks = 256 * 4;
@@ -858,17 +926,39 @@ static int launch_gcn_backward(int64_t n_tiles, hipStream_t st, const int32_t* p
     do {                                                                                                                                  \
         if (drop.thr != 0u)                                                                                                               \
             k_gcn_backward<M, K, H, WIDE, true><<<(unsigned)blocks, kGcnThreads, 0, st>>>(ptr, idx, val, n, D, self_coef, X, W, fuse_act, heavy, d_in, \
-                                                                                          colsum_in, partial_w, n_self, drop);          \
+                                                                                          colsum_in, partial_w, n_self, drop, nullptr, nullptr); \
         else                                                                                                                              \
             k_gcn_backward<M, K, H, WIDE, false><<<(unsigned)blocks, kGcnThreads, 0, st>>>(ptr, idx, val, n, D, self_coef, X, W, fuse_act, heavy, d_in, \
-                                                                                           colsum_in, partial_w, n_self, drop);         \
+                                                                                           colsum_in, partial_w, n_self, drop, nullptr, nullptr); \
     } while (0)
     if (cap)
         k_gcn_backward<M, K, false, false, false, true><<<(unsigned)blocks, kGcnThreads, 0, st>>>(ptr, idx, val, n, D, self_coef, X, W, fuse_act, heavy, d_in,
-                                                                                                 colsum_in, partial_w, n_self, drop);
+                                                                                                 colsum_in, partial_w, n_self, drop, nullptr, nullptr);
     else if (heavy.slot != nullptr) { if (wide) PP_BWD(true, true); else PP_BWD(true, false); }
     else { if (wide) PP_BWD(false, true); else PP_BWD(false, false); }
 #undef PP_BWD
+    return PP_OK;
+}
+
+// the kBelow variant (64 x 64): its own resident grid, smaller at 2 waves per SIMD
+static int launch_gcn_backward_below(int64_t n_tiles, hipStream_t st, const int32_t* ptr, const int32_t* idx, const float* val, int64_t n, const float* D,
+                                     const float* self_coef, const float* X, const float* W, const float* agg_below, float* colsum_in, float* partial_w,
+                                     float* partial_w_below, int64_t* blocks_out) {
+    static int resident_below = 0;
+    if (resident_below == 0) {
+        int per_cu = 0, dev = 0, cus = 0;
+        PP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_gcn_backward<64, 64, false, false, false, true, true>, kGcnThreads, 0));
+        PP_HIP(hipGetDevice(&dev));
+        PP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        resident_below = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 256);
+        if (resident_below > kGcnBackwardMaxBlocks) resident_below = (int)kGcnBackwardMaxBlocks;
+    }
+    const int64_t resident = shared_grid(resident_below);
+    int64_t blocks = ceil_div(n_tiles, kGcnWaves);
+    if (blocks > resident) blocks = resident;
+    *blocks_out = blocks;
+    k_gcn_backward<64, 64, false, false, false, true, true><<<(unsigned)blocks, kGcnThreads, 0, st>>>(
+        ptr, idx, val, n, D, self_coef, X, W, 1, HeavyRows{nullptr, nullptr}, nullptr, colsum_in, partial_w, n, DropSite{}, agg_below, partial_w_below);
     return PP_OK;
 }
 
@@ -1024,6 +1114,44 @@ int pp_gcn_backward_nnz_f32(const int32_t* ptr, const int32_t* idx, const float*
     if (rc != PP_OK) return rc;
     PP_LAUNCH_CHECK();
     return pp::weight_grad_reduce((const float*)ws, nullptr, blocks, M, K, dW, nullptr, st);
+}
+
+size_t pp_gcn_backward_below_ws_bytes(int64_t n_rows) { return 2 * pp_gcn_backward_ws_bytes(n_rows); }      // two sets of partial tiles
+
+int pp_gcn_backward_below_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, int64_t n_self, int64_t nnz, const float* D, int M,
+                              const float* self_coef, const float* X, int K, const float* W, int fuse_act, const int32_t* heavy_slot,
+                              const float* heavy_sum, float* d_in, float* colsum_in, float* dW, void* ws, size_t ws_bytes, double drop_p,
+                              int64_t drop_seed, int64_t drop_tag, int64_t drop_row0, const float* agg_below, int K_below, float* dW_below,
+                              pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    (void)nnz; (void)heavy_sum; (void)d_in; (void)drop_seed; (void)drop_tag; (void)drop_row0;      // (d_in is not formed: it may be NULL)
+    PP_REQUIRE(M == 64 && K == 64 && K_below == 64, PP_ERR_ARG, "pp_gcn_backward_below_f32: 64 x 64 layers only (got %dx%d over %d)", M, K, K_below);
+    PP_REQUIRE(fuse_act != 0 && colsum_in != nullptr, PP_ERR_ARG, "pp_gcn_backward_below_f32: fuse_act and colsum_in are required");
+    PP_REQUIRE(n_rows >= 0 && n_self == n_rows, PP_ERR_ARG, "pp_gcn_backward_below_f32: whole graphs only (n_self == n_rows)");
+    PP_REQUIRE(heavy_slot == nullptr, PP_ERR_ARG, "pp_gcn_backward_below_f32: no variant with hub rows");
+    PP_REQUIRE(drop_p == 0.0, PP_ERR_ARG, "pp_gcn_backward_below_f32: no variant with dropout");
+    PP_REQUIRE(dW != nullptr && dW_below != nullptr && (n_rows == 0 || agg_below != nullptr), PP_ERR_ARG,
+               "pp_gcn_backward_below_f32: dW, dW_below and agg_below are required");
+    PP_REQUIRE(((uintptr_t)D | (uintptr_t)X | (uintptr_t)agg_below) % 16 == 0, PP_ERR_ARG, "pp_gcn_backward_below_f32: D, X and agg_below must be 16-byte aligned");
+    const bool wide = (uint64_t)n_rows * 64u * 4u >= (uint64_t)pp::kBufOob || n_rows >= ((int64_t)1 << 30) - 64;
+    PP_REQUIRE(!wide, PP_ERR_ARG, "pp_gcn_backward_below_f32: the matrices must fit 32-bit byte offsets");
+    PP_REQUIRE(ws_bytes >= pp_gcn_backward_below_ws_bytes(n_rows), PP_ERR_WORKSPACE, "pp_gcn_backward_below_f32: workspace too small");
+    PP_HIP(hipMemsetAsync(colsum_in, 0, 64 * sizeof(float), st));
+    if (n_rows == 0) {
+        PP_HIP(hipMemsetAsync(dW, 0, 64 * 64 * sizeof(float), st));
+        PP_HIP(hipMemsetAsync(dW_below, 0, 64 * 64 * sizeof(float), st));
+        return PP_OK;
+    }
+    float* pw = (float*)ws;
+    float* pw_below = (float*)((char*)ws + pp_gcn_backward_ws_bytes(n_rows));
+    int64_t blocks = 0;
+    const int rc = pp::launch_gcn_backward_below(pp::ceil_div(n_rows, 16), st, ptr, idx, val, n_rows, D, self_coef, X, W, agg_below, colsum_in, pw, pw_below,
+                                                 &blocks);
+    if (rc != PP_OK) return rc;
+    PP_LAUNCH_CHECK();
+    const int rc_w = pp::weight_grad_reduce(pw, nullptr, blocks, 64, 64, dW, nullptr, st);
+    if (rc_w != PP_OK) return rc_w;
+    return pp::weight_grad_reduce(pw_below, nullptr, blocks, 64, 64, dW_below, nullptr, st);
 }
 
 }  // extern "C"

@@ -26,6 +26,8 @@ from .. import _hip
 TAG_FO, TAG_FO_OUT, TAG_HO, TAG_HO_OUT, TAG_HEAD = 0, 32, 64, 96, 128          # dropout call sites (same numbering as nn.dbgnn)
 OWNED_ROW_BACKWARD = True          # _ShardedTrunk: exchange A^T dpre and run the layer's GEMMs on the owned rows only (False: the fused kernel over
 #                                    owned + halo rows, then exchange of its output — kept for A/B measurements, bench.py --halo-row-backward)
+FUSE_FIRST_DW = True               # _ShardedGcnStack (world size 1): layer 1's backward kernel also forms layer 0's weight gradient and never stores
+#                                    d_in (pp_gcn_backward_below_f32; False: gcn_backward + weight_grad, the same results from one kernel more)
 
 
 class HipOps:
@@ -131,6 +133,19 @@ class HipOps:
             d_lin, colsum = _hip.act_backward(d_lin, fuse_below, True, want_dpre=True, want_dbias=True)
             return d_lin, colsum, dw
         return d_lin, None, dw
+
+    # ---- backward of layer 1 together with the weight gradient of layer 0 (whose input takes no gradient): d_in is never stored
+    @staticmethod
+    def backward_below_ok(plan, weight: torch.Tensor, agg_below) -> bool:
+        """64/64/64 widths on a whole graph with short rows (the rule of the register-capped backward kernel) and without hub rows."""
+        return (agg_below is not None and tuple(weight.shape) == (64, 64) and agg_below.size(1) == 64 and plan.bwd_heavy is None
+                and plan.bwd_idx.numel() <= 8 * plan.n_src and plan.n_dst == plan.n_src)
+
+    @staticmethod
+    def layer_backward_below(plan, dpre: torch.Tensor, x_in: torch.Tensor, weight: torch.Tensor, agg_below: torch.Tensor):
+        """``(colsum, dW, dW_below)``: :meth:`layer_backward` with ``fuse_below`` followed by the weight gradient of the layer below from
+        its kept ``A x``, in one kernel (needs :meth:`backward_below_ok`)."""
+        return _hip.gcn_backward_below(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, plan.n_src, dpre, plan.self_coef, x_in, weight, agg_below)
 
     # ---- backward of a layer with the matrix work on the OWNED rows only (world size > 1): the halo rows' partial sums A^T dpre travel back
     # to their owners BEFORE the product with W, so both GEMMs of the layer (input gradient, weight gradient) run once per row
@@ -414,6 +429,11 @@ class _ShardedGcnStack(torch.autograd.Function):
             x_in = ctx.inputs[layer]
             if layer == 0:
                 grads[0] = ops.layer_backward(plan, d, x_in, weight, ctx.saved[0], False, None)[2]
+                break
+            if (layer == 1 and FUSE_FIRST_DW and comm.world == 1 and ctx.drop is None and ctx.saved[0] is not None
+                    and getattr(ops, "backward_below_ok", lambda p_, w_, a_: False)(plan, weight, ctx.saved[0])):
+                # layer 0 needs nothing but its weight and bias gradients: both leave the kernel of layer 1, d_in is not stored
+                grads[1], grads[2], grads[0] = ops.layer_backward_below(plan, d, x_in, weight, ctx.saved[0])
                 break
             # world size 1: the input IS the stored (possibly dropped) activation of the layer below, its backward rides in the same kernel
             fuse_below = x_in if (comm.world == 1 and (ctx.drop is None or ops.drop_fusable(weight))) else None

@@ -123,6 +123,12 @@ def main():
         xa = torch.nn.functional.elu(torch.randn(n_ho, f, device=dev))
         if narrow:
             report("gcn_backward fused (gather + d_in + ELU' + colsum + dW)", lambda: _hip.gcn_backward(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, n_ho, dpre, plan.self_coef, xa, wq, True, True))
+            if f == 64 and nnz <= 8 * n_ho:
+                ax = torch.randn(n_ho, f, device=dev)              # (stands for the A x the first layer's forward kernel keeps)
+                bw = (plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, n_ho, dpre, plan.self_coef, xa, wq)
+                report("gcn_backward + first-layer dW, one kernel", lambda: _hip.gcn_backward_below(*bw, ax))
+                report("gcn_backward + weight_grad (what it replaces)", lambda: _hip.weight_grad(_hip.gcn_backward(*bw, True, True)[0], ax, False))
+                del ax, bw
             report("spmm bwd + dense_backward (what it replaces)", lambda: _hip.dense_backward(_hip.spmm(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, n_ho, dpre, plan.self_coef, dpre), xa, wq, True, True, True, False))
         else:
             report("gcn_input_grad fused (gather + d_in + ELU' + colsum)", lambda: _hip.gcn_input_grad(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, n_ho, dpre, plan.self_coef, wq, xa, True), alg + 4 * f * n_ho / 1e9)
