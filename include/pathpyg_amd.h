@@ -595,6 +595,29 @@ int pp_dense_narrow_supported(int P, int Q);
 int pp_dense_narrow_f32(const float* A, const float* W, int w_transposed, int64_t n_rows, int P, int Q, const float* bias, const float* grad_act,
                         float* colsum, float* out, pp_stream_t stream);
 
+/* The head of the DBGNN on the first-order rows (pp_head.hip): everything between the bipartite sum and the bipartite backward —
+ * BipartiteGraphOperator after the re-association of lin1, its ELU and the classifier (reference nn/dbgnn.py:66-69,143-151):
+ *   z      = ELU( agg . W1^T + deg (*) (x . W2^T + b2 + b1) )     agg [n,Ha] = summed higher-order rows, x [n,Hx] = stored ELU activation of the
+ *   logits = z . Wlin^T + blin                                    first-order stack, deg [n] = bipartite in-degree; W1 [Hb,Ha], W2 [Hb,Hx], Wlin [C,Hb]
+ * in ONE kernel (z [n,Hb] is stored for the backward, logits [n,C]); the products agg . W1^T and x . W2^T and the pre-activation never
+ * reach memory.  pp_dbgnn_head_supported: Ha, Hx, Hb in {16, 32, 64} and 1 <= C <= 16; anything else is PP_ERR_ARG. */
+int pp_dbgnn_head_supported(int Ha, int Hx, int Hb, int C);
+int pp_dbgnn_head_forward_f32(const float* agg, const float* x, const float* deg, const float* W1, const float* b1, const float* W2, const float* b2,
+                              const float* Wlin, const float* blin, int64_t n_rows, int Ha, int Hx, int Hb, int C, float* z, float* logits,
+                              pp_stream_t stream);
+/* Its backward (autograd of the same lines), per 16-row tile in registers:  dz = dlogits . Wlin,  dpre = dz (*) ELU'(z),  dper = deg (*) dpre,
+ *   d_agg [n,Ha]   = dpre . W1                        (gradient of the bipartite sum)
+ *   dpre_fo [n,Hx] = (dper . W2) (*) ELU'(x)          (gradient w.r.t. the PRE-activation of the first-order stack's last layer, as the
+ *   colsum_fo [Hx] = column sums of dpre_fo            gradient epilogue of pp_dense_f32 / pp_dense_backward_f32 hands it down; = that layer's bias gradient)
+ *   dW1 [Hb,Ha] = dpre^T agg,  dW2 [Hb,Hx] = dper^T x,  db1 = db2 [Hb] = column sums of dper,  dWlin [C,Hb] = dlogits^T z,  dblin [C] = column sums of dlogits.
+ * dz, dpre and dper never reach memory.  The weight gradients are per-workgroup partial tiles summed in a fixed order (as pp_dense_backward_f32);
+ * ws: pp_dbgnn_head_backward_ws_bytes(n_rows). */
+size_t pp_dbgnn_head_backward_ws_bytes(int64_t n_rows);
+int pp_dbgnn_head_backward_f32(const float* dlogits, const float* z, const float* agg, const float* x, const float* deg, const float* W1,
+                               const float* W2, const float* Wlin, int64_t n_rows, int Ha, int Hx, int Hb, int C, float* d_agg,
+                               float* dpre_fo, float* colsum_fo, float* dW1, float* dW2, float* db1, float* db2, float* dWlin, float* dblin,
+                               void* ws, size_t ws_bytes, pp_stream_t stream);
+
 /* All-pairs shortest time-respecting paths (temporal_shortest_paths, src/pathpyG/algorithms/temporal.py:57-107: scipy Dijkstra with
  * unit weights on the event DAG augmented by a virtual source and sink per node) as a frontier BFS per source node on the event graph:
  *   edge_index [2,m] time-sorted events;  succ_ptr [m+1] / succ [E2]: CSR of lift_order_temporal's result (row i -> events j);

@@ -1593,3 +1593,54 @@ def dense_backward(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, fuse
         check(L.pp_dense_backward_f32(_p(dy), _p(x), _p(weight), n, m, k, 1 if fuse_act else 0, _p(d_in), _p(colsum), _p(dw), _p(db),
                                       _p(ws), ws.numel(), _stream()), "pp_dense_backward_f32")
     return d_in, colsum, dw, db
+
+
+def head_supported(ha: int, hx: int, hb: int, c: int) -> bool:
+    """Whether the fused DBGNN head (:func:`head_forward` / :func:`head_backward`) takes these widths: ``agg`` [n, ha], ``x`` [n, hx],
+    bipartite width ``hb`` (each 16, 32 or 64) and ``c`` <= 16 classes."""
+    return bool(lib().pp_dbgnn_head_supported(ha, hx, hb, c))
+
+
+def head_forward(agg: torch.Tensor, x: torch.Tensor, deg: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                 wlin: torch.Tensor, blin: torch.Tensor):
+    """``z = ELU(agg @ w1.T + deg[:, None] * (x @ w2.T + b2 + b1))`` and ``logits = z @ wlin.T + blin`` in one kernel
+    (pp_dbgnn_head_forward_f32): ``(z, logits)``.  Shapes must satisfy :func:`head_supported`."""
+    dev = require_device(agg, x, deg, w1, b1, w2, b2, wlin, blin)
+    agg, x, deg = agg.contiguous(), x.contiguous(), deg.to(torch.float32).contiguous()
+    w1, b1, w2, b2, wlin, blin = (t.contiguous() for t in (w1, b1, w2, b2, wlin, blin))
+    n, ha = agg.shape
+    hx, hb, c = x.size(1), w1.size(0), wlin.size(0)
+    if (agg.dtype != torch.float32 or x.dtype != torch.float32 or x.size(0) != n or deg.numel() != n or tuple(w1.shape) != (hb, ha)
+            or tuple(w2.shape) != (hb, hx) or wlin.size(1) != hb or b1.numel() != hb or b2.numel() != hb or blin.numel() != c):
+        raise ValueError("head_forward: agg [n, Ha], x [n, Hx], deg [n], w1 [Hb, Ha], w2 [Hb, Hx], wlin [C, Hb] (fp32) and their biases expected")
+    with torch.cuda.device(dev):
+        z = torch.empty((n, hb), dtype=torch.float32, device=dev)
+        logits = torch.empty((n, c), dtype=torch.float32, device=dev)
+        check(lib().pp_dbgnn_head_forward_f32(_p(agg), _p(x), _p(deg), _p(w1), _p(b1), _p(w2), _p(b2), _p(wlin), _p(blin), n, ha, hx, hb, c,
+                                              _p(z), _p(logits), _stream()), "pp_dbgnn_head_forward_f32")
+    return z, logits
+
+
+def head_backward(dlogits: torch.Tensor, z: torch.Tensor, agg: torch.Tensor, x: torch.Tensor, deg: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor,
+                  wlin: torch.Tensor, want_colsum: bool = True):
+    """Backward of :func:`head_forward` (pp_dbgnn_head_backward_f32): ``(d_agg, dpre_fo, colsum_fo or None, dW1, dW2, db1, db2, dWlin, dblin)``
+    with ``dpre_fo`` the gradient w.r.t. the PRE-activation behind ``x`` and ``colsum_fo`` its column sums (that layer's bias gradient)."""
+    dev = require_device(dlogits, z, agg, x, deg, w1, w2, wlin)
+    dlogits, z, agg, x, deg = dlogits.contiguous(), z.contiguous(), agg.contiguous(), x.contiguous(), deg.to(torch.float32).contiguous()
+    w1, w2, wlin = w1.contiguous(), w2.contiguous(), wlin.contiguous()
+    n, ha = agg.shape
+    hx, hb, c = x.size(1), w1.size(0), wlin.size(0)
+    if tuple(dlogits.shape) != (n, c) or tuple(z.shape) != (n, hb) or x.size(0) != n or deg.numel() != n or dlogits.dtype != torch.float32:
+        raise ValueError("head_backward: dlogits [n, C], z [n, Hb], agg [n, Ha], x [n, Hx] (fp32) and deg [n] expected")
+    L = lib()
+    with torch.cuda.device(dev):
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_agg, dpre_fo = torch.empty((n, ha), **f32), torch.empty((n, hx), **f32)
+        colsum = torch.empty(hx, **f32) if want_colsum else None
+        dw1, dw2, dwlin = torch.empty((hb, ha), **f32), torch.empty((hb, hx), **f32), torch.empty((c, hb), **f32)
+        db1, db2, dblin = torch.empty(hb, **f32), torch.empty(hb, **f32), torch.empty(c, **f32)
+        ws = _workspace(L.pp_dbgnn_head_backward_ws_bytes(n), dev)
+        check(L.pp_dbgnn_head_backward_f32(_p(dlogits), _p(z), _p(agg), _p(x), _p(deg), _p(w1), _p(w2), _p(wlin), n, ha, hx, hb, c,
+                                           _p(d_agg), _p(dpre_fo), _p(colsum), _p(dw1), _p(dw2), _p(db1), _p(db2), _p(dwlin), _p(dblin), _p(ws), ws.numel(), _stream()),
+              "pp_dbgnn_head_backward_f32")
+    return d_agg, dpre_fo, colsum, dw1, dw2, db1, db2, dwlin, dblin

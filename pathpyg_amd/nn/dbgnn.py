@@ -254,6 +254,45 @@ def bip_combine(agg_lin, per_node, deg, bias):
     return _BipCombine.apply(agg_lin, per_node, deg, bias)
 
 
+FUSE_HEAD = True                   # head(): bipartite combine + classifier as ONE kernel each way (pp_dbgnn_head_forward_f32 / _backward_f32; False: the
+#                                    chain dense_w, dense, bip_combine, dense and its backward kernels — the same results through five n x 64 intermediates)
+
+
+class _Head(torch.autograd.Function):
+    """``logits = lin(ELU(agg W1^T + deg * (x W2^T + b2 + b1)))``: everything between the bipartite sum and the loss (reference
+    nn/dbgnn.py:66-69,143-151 after the re-association of lin1) in ONE kernel; ``z`` is the only intermediate that is stored.  ``x`` is the stored
+    activation of the first-order stack, whose last layer follows the ``grad_is_pre`` contract: the backward kernel hands back the gradient
+    w.r.t. its PRE-activation and its bias gradient (as the gradient of ``act_bias``), exactly as ``dense(x, lin2, True, act_bias)`` does."""
+
+    @staticmethod
+    def forward(ctx, agg, x, deg, w1, b1, w2, b2, wlin, blin, act_bias):
+        z, logits = _hip.head_forward(agg, x, deg, w1, b1, w2, b2, wlin, blin)
+        ctx.save_for_backward(z, agg, x, deg, w1, w2, wlin)
+        ctx.has_act_bias = act_bias is not None
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        z, agg, x, deg, w1, w2, wlin = ctx.saved_tensors
+        want_sum = ctx.has_act_bias and ctx.needs_input_grad[9]
+        d_agg, dpre_fo, colsum, dw1, dw2, db1, db2, dwlin, dblin = _hip.head_backward(dlogits, z, agg, x, deg, w1, w2, wlin, want_sum)
+        return d_agg, dpre_fo, None, dw1, db1, dw2, db2, dwlin, dblin, colsum
+
+
+def head(agg, x, deg, bipartite_layer, lin: Linear, act_bias):
+    """The model's head on the first-order rows: ``lin(ELU(lin1.weight agg + deg * (lin2(x) + lin1.bias)))`` with ``agg`` the bipartite sum of
+    the higher-order rows and ``x`` / ``act_bias`` the first-order stack's stored activation and the bias behind it (contract of :class:`_Dense`
+    with ``fuse_act``).  One kernel each way where :data:`FUSE_HEAD` is on, all three layers have a bias and the widths are ones the kernel
+    takes (``_hip.head_supported``); the chain of dense / combine kernels otherwise."""
+    bl = bipartite_layer
+    if (FUSE_HEAD and bl.lin1.bias is not None and bl.lin2.bias is not None and lin.bias is not None
+            and agg.dim() == 2 and x.dim() == 2 and agg.is_cuda and x.is_cuda and agg.dtype == x.dtype == torch.float32
+            and bl.lin1.weight.size(1) == agg.size(1) and bl.lin2.weight.size(1) == x.size(1) and lin.weight.size(1) == bl.lin1.weight.size(0)
+            and _hip.head_supported(agg.size(1), x.size(1), bl.lin1.weight.size(0), lin.weight.size(0))):
+        return _Head.apply(agg, x, deg, bl.lin1.weight, bl.lin1.bias, bl.lin2.weight, bl.lin2.bias, lin.weight, lin.bias, act_bias)
+    return dense(bip_combine(dense_w(agg, bl.lin1.weight), dense(x, bl.lin2, True, act_bias), deg, bl.lin1.bias), lin)
+
+
 class _DropAct(torch.autograd.Function):
     """Training-mode dropout of a matrix whose rows are the GLOBAL rows ``row0 .. row0 + n`` (or ``rows``), with the counter-based masks of
     ``pp_dropout_f32`` (no mask tensor; the same decision for the same (seed, tag, row, column) on every rank of a partitioned run).
@@ -611,8 +650,7 @@ class DBGNN(Module):
             # x_h), then everything else lives on the N first-order rows (N << U) — instead of a dense layer over all U rows
             # forward and its three-matrix backward.  Same sum, re-associated (linearity of lin1).
             agg = _AggregateAct.apply(plan_bi, x_h, bias_ho)
-            # (dense(): its weight gradients contract over all N rows on the MFMA kernel; the library GEMM is 4x slower there)
-            x = bip_combine(dense_w(agg, bl.lin1.weight), dense(x, bl.lin2, True, bias_fo), plan_bi.self_coef, bl.lin1.bias)
-            return dense(x, self.lin)
+            # (head(): one kernel each way; its fallback chain's dense() contracts the weight gradients over all N rows on the MFMA kernel)
+            return head(agg, x, plan_bi.self_coef, bl, self.lin, bias_fo)
         x = _Propagate.apply(plan_bi, dense(x_h, bl.lin1, True, bias_ho), dense(x, bl.lin2, True, bias_fo), None, True, True)
         return dense(x, self.lin, True, None)

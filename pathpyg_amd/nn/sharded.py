@@ -251,6 +251,14 @@ class HipOps:
         return bip_combine(agg_lin, per_node, deg, bias)
 
     @staticmethod
+    def head(agg, x, deg, bipartite_layer, lin, act_bias):
+        """Bipartite combine + classifier on the owned first-order rows: one kernel each way (pp_dbgnn_head_forward_f32 / _backward_f32)
+        where ``nn.dbgnn.FUSE_HEAD`` and the shapes allow it, the chain of :meth:`dense_nobias` / :meth:`dense` / :meth:`bip_combine`
+        otherwise (``nn.dbgnn.head``)."""
+        from .dbgnn import head
+        return head(agg, x, deg, bipartite_layer, lin, act_bias)
+
+    @staticmethod
     def cross_entropy_mean(logits, target):
         from .dbgnn import cross_entropy
         return cross_entropy(logits, target)
@@ -710,6 +718,7 @@ class ShardedDBGNN(torch.nn.Module):
             return _ShardedGcnStack.apply(graph_shard, comm, ops, drop, x_full, *params), layers[-1].bias
 
         bl = m.bipartite_layer
+        head = getattr(ops, "head", None)       # (the CPU stand-ins of the distributed tests have none: they run the chain below)
         if comm.world > 1:
             shard.resolve()
         if comm.world > 1 and not dropping and len(m.first_order_layers) == len(m.higher_order_layers) and self.overlap:
@@ -719,6 +728,8 @@ class ShardedDBGNN(torch.nn.Module):
                 for layer in layers:
                     params += [layer.lin.weight, layer.bias]
             x, agg = _ShardedTrunk.apply(shard, comm, ops, len(m.first_order_layers), *params)
+            if head is not None:
+                return head(agg, x, shard.indeg, bl, m.lin, m.first_order_layers[-1].bias)
             x = ops.bip_combine(ops.dense_nobias(agg, bl.lin1.weight), ops.dense(x, bl.lin2, True, m.first_order_layers[-1].bias), shard.indeg,
                                 bl.lin1.bias)
             return ops.dense(x, m.lin)
@@ -737,6 +748,8 @@ class ShardedDBGNN(torch.nn.Module):
             return ops.dense(ops.drop_act(x, None, p, seed, TAG_HEAD, shard.fo.lo, False), m.lin)
         # sum_j (W1 y_h[j] + b1) = W1 (sum_j y_h[j]) + deg * b1 (linearity, as in DBGNN.forward): only [N, H] partials cross xGMI
         agg = _ShardedBipartite.apply(shard.bip, comm, ops, shard.cap, shard.fo.n_own, x_h, bias_ho)
+        if head is not None:
+            return head(agg, x, shard.indeg, bl, m.lin, bias_fo)
         x = ops.bip_combine(ops.dense_nobias(agg, bl.lin1.weight), ops.dense(x, bl.lin2, True, bias_fo), shard.indeg, bl.lin1.bias)
         return ops.dense(x, m.lin)
 
