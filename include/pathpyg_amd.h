@@ -56,6 +56,8 @@ const char* pp_last_error(void);
  * workgroups that are resident at once, which leaves no slot for a kernel of another stream.  pp_set_launch_share(s) lets the persistent
  * launches of the CALLING THREAD take only s per mille of those slots (1..1000, default 1000) and returns the previous value. */
 int pp_set_launch_share(int per_mille);
+/* workgroups of the calling thread's most recent persistent launch (0 before the first one) */
+int64_t pp_last_persistent_grid(void);
 
 /* ------------------------------------------------------------------ primitives (pp_scan.hip, pp_sort.hip) */
 

@@ -7,6 +7,7 @@ happens in the HIP kernels.  There is no CPU implementation behind these calls.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import threading
 
@@ -29,6 +30,23 @@ def _stream() -> int:
     if _raw_stream is not None:
         return _raw_stream(torch.cuda.current_device())
     return torch.cuda.current_stream().cuda_stream
+
+
+@contextlib.contextmanager
+def launch_share(per_mille: int):
+    """Persistent launches inside the block take ``per_mille`` / 1000 of the resident workgroup slots (pp_set_launch_share; never fewer
+    than 8 workgroups); the previous share comes back on exit.  The share belongs to the CALLING THREAD: autograd runs backward on a
+    thread of its own, which keeps its own share, so only the wrappers called directly inside the block are affected."""
+    before = lib().pp_set_launch_share(int(per_mille))
+    try:
+        yield
+    finally:
+        lib().pp_set_launch_share(before)
+
+
+def last_persistent_grid() -> int:
+    """Workgroups of the calling thread's most recent persistent launch (the kernels whose grid :func:`launch_share` shrinks)."""
+    return int(lib().pp_last_persistent_grid())
 
 
 def _p(t: torch.Tensor | None):

@@ -512,6 +512,7 @@ static int launch_gcn_forward(int64_t n_tiles, hipStream_t st, const GcnArgs& a)
     int64_t blocks = ceil_div(n_tiles, kThreads / kWave);
     if (blocks > resident) blocks = resident;
     else blocks = (blocks + 7) / 8 * 8;                                 // (a multiple of the 8 XCDs: the kernel's tile order wants whole dies)
+    note_persistent_grid(blocks);
 #define PP_FWD(H, WIDE)                                                                                                                  \
     do {                                                                                                                                  \
         if (a.drop.thr != 0u)                                                                                                             \
@@ -922,6 +923,7 @@ static int launch_gcn_backward(int64_t n_tiles, hipStream_t st, const int32_t* p
     int64_t blocks = ceil_div(n_tiles, kGcnWaves);
     if (blocks > resident) blocks = resident;
     *blocks_out = blocks;
+    note_persistent_grid(blocks);
 #define PP_BWD(H, WIDE)                                                                                                                  \
     do {                                                                                                                                  \
         if (drop.thr != 0u)                                                                                                               \
@@ -957,6 +959,7 @@ static int launch_gcn_backward_below(int64_t n_tiles, hipStream_t st, const int3
     int64_t blocks = ceil_div(n_tiles, kGcnWaves);
     if (blocks > resident) blocks = resident;
     *blocks_out = blocks;
+    note_persistent_grid(blocks);
     k_gcn_backward<64, 64, false, false, false, true, true><<<(unsigned)blocks, kGcnThreads, 0, st>>>(
         ptr, idx, val, n, D, self_coef, X, W, 1, HeavyRows{nullptr, nullptr}, nullptr, colsum_in, partial_w, n, DropSite{}, agg_below, partial_w_below);
     return PP_OK;

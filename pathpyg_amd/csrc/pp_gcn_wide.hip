@@ -177,7 +177,10 @@ __global__ __launch_bounds__(kWideThreads, PP_WIDE_OCC) void k_wide_layer(const 
                     const int64_t r = tr + rt;
                     p0[q] = __shfl(pv, rt, kWave);
                     hs[q] = __shfl(hv, rt, kWave);
-                    p1[q] = hs[q] >= 0 ? p0[q] : __shfl(pv, rt + 1, kWave);      // a hub row: its neighbour sum is already in heavy.sum
+                    // (the shuffle stays outside the conditional: lane rt + 1 may belong to ANOTHER lane group, and a shuffle that only the
+                    // lanes of ordinary rows execute reads nothing from the lanes of a hub row, which sit out that branch)
+                    const int pn = __shfl(pv, rt + 1, kWave);
+                    p1[q] = hs[q] >= 0 ? p0[q] : pn;                               // a hub row: its neighbour sum is already in heavy.sum
                     sc[q] = __shfl(scv, rt, kWave);
                     const bool self_here = r < n_self && (dense || self_coef != nullptr);
                     const int first = __shfl(cj4, 4 * rt, kWave);
@@ -670,6 +673,7 @@ static int launch_wide(hipStream_t st, const WideArgs& a) {
     }
     int64_t blocks = ceil_div(ceil_div(a.n_rows, 16), kWideWaves);
     if (blocks > shared_grid(resident)) blocks = shared_grid(resident);
+    note_persistent_grid(blocks);
     k_wide_layer<P, Q, kEpi><<<(unsigned)blocks, kWideThreads, 0, st>>>(a.ptr, a.idx, a.val, a.n_rows, a.n_self, a.X, a.self_coef, a.Wr, a.bias, a.act,
                                                                          a.heavy, a.agg_out, a.Y, a.act_in, a.colsum);
     PP_LAUNCH_CHECK();
@@ -698,6 +702,7 @@ static int launch_wide_ws(hipStream_t st, const WideArgs& a) {
     }
     int64_t blocks = ceil_div(a.n_rows, kWsTile);
     if (blocks > shared_grid(cus)) blocks = shared_grid(cus);
+    note_persistent_grid(blocks);
     k_wide_ws<kEpi><<<(unsigned)blocks, kWsThreads, 0, st>>>(a.ptr, a.idx, a.val, a.n_rows, a.n_self, a.X, a.self_coef, a.Wr, a.bias, a.act, a.heavy,
                                                              a.agg_out, a.Y, a.act_in, a.colsum);
     PP_LAUNCH_CHECK();
@@ -913,6 +918,8 @@ static int launch_gemm(hipStream_t st, const WideArgs& a) {
     }
     int64_t blocks = ceil_div(a.n_rows, ROWS);
     if (blocks > cus) blocks = cus;                       // one 1024-thread workgroup (74 - 92 KB of LDS) per CU
+    if (blocks > shared_grid(cus)) blocks = shared_grid(cus);
+    note_persistent_grid(blocks);
     k_dense_lds<P, Q, kEpi><<<(unsigned)blocks, kGemmThreads, 0, st>>>(a.X, a.n_rows, a.Wr, a.bias, a.act, a.Y, a.act_in, a.colsum);
     PP_LAUNCH_CHECK();
     return PP_OK;

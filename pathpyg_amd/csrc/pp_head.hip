@@ -417,7 +417,9 @@ static inline int64_t head_blocks(int64_t n_rows, int resident, int64_t cap) {
     int64_t blocks = ceil_div(ceil_div(n_rows > 0 ? n_rows : 1, 16), kWavesPerBlock);
     const int64_t share = shared_grid(resident);
     if (blocks > share) blocks = share;
-    return blocks > cap ? cap : blocks;
+    if (blocks > cap) blocks = cap;
+    note_persistent_grid(blocks);
+    return blocks;
 }
 
 template <int HA, int HX, int HB>

@@ -12,6 +12,8 @@ static inline int64_t shared_grid(int64_t resident) {
     const int64_t g = resident * launch_share_permille() / 1000;
     return g < 8 ? 8 : g / 8 * 8;
 }
+// Every launcher that sizes a grid through shared_grid records the workgroups it launched (pp_last_persistent_grid, per thread).
+void note_persistent_grid(int64_t blocks);
 size_t scan_ws_bytes(int64_t n);
 template <typename InT, typename OutT>
 int exclusive_scan(const InT* in, int64_t n, OutT* out, bool with_total, int64_t* total_dev, void* ws, size_t ws_bytes,

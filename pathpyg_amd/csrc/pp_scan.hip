@@ -12,7 +12,9 @@ namespace pp {
 
 static thread_local char g_err[512] = "";
 static thread_local int g_launch_share = 1000;
+static thread_local int64_t g_last_persistent_grid = 0;
 int launch_share_permille() { return g_launch_share; }
+void note_persistent_grid(int64_t blocks) { g_last_persistent_grid = blocks; }
 void set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -401,6 +403,7 @@ int pp_set_launch_share(int per_mille) {
     pp::g_launch_share = per_mille < 1 ? 1 : (per_mille > 1000 ? 1000 : per_mille);
     return before;
 }
+int64_t pp_last_persistent_grid(void) { return pp::g_last_persistent_grid; }
 
 size_t pp_scan_ws_bytes(int64_t n) { return pp::scan_ws_bytes(n); }
 

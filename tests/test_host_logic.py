@@ -341,3 +341,17 @@ def test_order2_builder_is_not_chosen_for_contact_shaped_streams():
     assert _hip.debruijn2_wanted(2 * 10**7, 10**6)              # BASELINE configs[2]'s scale-free generator (one node with 2 * 10^6 in-events)
     assert _hip.debruijn2_wanted(28_561, 126)                   # the size of the reference's documented contact datasets: 227 events per node
     assert not _hip.debruijn2_wanted(2 * 10**6, 96)             # 96 nodes / 2 * 10^6 events: every node a hub on both sides
+
+
+def test_small_grid_cases_are_exact_in_fp32():
+    """Every case of tests/test_gpu_small_grid.py, built here without a GPU: each linear output is a multiple of its common denominator and
+    the sum of the magnitudes of its terms times that denominator stays below 2^24 (the generators assert it, thinning their gradients
+    where a sum over all rows needs it), so the fp32 kernels must reproduce the float64 values bit for bit."""
+    from tests import small_grid_cases as sg
+    built = 0
+    for case_id, build in sg.all_cases():
+        case = build()
+        assert 0.0 < case.ratio < 1.0, case_id
+        assert all(value.abs().max() > 0 for outputs in case.exact.values() for value, _, _ in outputs.values()), case_id
+        built += 1
+    assert built > 600
