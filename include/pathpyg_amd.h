@@ -479,7 +479,10 @@ int pp_dense_f32(const float* A, const float* W, int w_transposed, int64_t n_row
                  const float* grad_act, float* colsum, float* out, void* ws, size_t ws_bytes, pp_stream_t stream);
 
 /* Mean softmax cross-entropy of logits [n,C] (C <= 64) against int64 targets [n] and its gradient dlogits [n,C] (may be NULL) in
- * one pass - the loss of the train step bench.py times (the reference ships no training loop). */
+ * one pass - the loss of the train step bench.py times (the reference ships no training loop).  Per row, with m = z[a] the
+ * row maximum:  loss_i = (m - z[y]) + log1p(sum_{c != a} exp(z[c] - m))  - F.cross_entropy's value without the saturation of
+ * -log(softmax[y]) at large spreads and without the cancellation of m + log(sum) - z[y] on confident rows; a target on a class masked
+ * with -inf gives +inf, and dlogits is exactly 0 in masked columns. */
 size_t pp_cross_entropy_ws_bytes(void);       /* per-workgroup partial sums, added in a fixed order: the loss is bitwise reproducible */
 int pp_cross_entropy_f32(const float* logits, const int64_t* target, int64_t n, int C, float* loss, float* dlogits, void* ws, size_t ws_bytes,
                          pp_stream_t stream);

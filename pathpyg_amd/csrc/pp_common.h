@@ -250,6 +250,8 @@ struct HeavyRows {
 // ELU(x) = x > 0 ? x : exp(x) - 1, branch-free and cheap (libm's expm1f is ~40 instructions and branches): on (-0.25, 0] the
 // degree-6 Taylor polynomial of expm1 (truncation < 5e-8 relative), below that v_exp_f32 - 1 (the result is <= -0.22, so the 1-ulp
 // error of the exponential stays < 3e-7 relative).  The two-lane form runs the polynomial on packed fp32 (v_pk_fma_f32).
+// Measured on an MI355X against float64 expm1, through every forward entry point, on a grid from -2^-100 to -100 with -0.25 and its two
+// fp32 neighbours (tests/test_gpu_value_domain.py): 9.3e-8 relative on the polynomial branch, 1.2e-7 on the exponential one.
 using pp_f32x2 = __attribute__((ext_vector_type(2))) float;
 
 __device__ __forceinline__ pp_f32x2 elu_fast2(pp_f32x2 x) {

@@ -1715,7 +1715,10 @@ int pp_dense_f32(const float* A, const float* W, int w_transposed, int64_t n_row
 // =====================================================================================================
 // Softmax cross-entropy over node logits, forward AND gradient in one pass (the train step's loss; the reference has no
 // training loop of its own).  One lane per row (C <= 64 classes kept in registers), mean reduction:
-//   loss = mean_i( logsumexp(z_i) - z_i[y_i] ),   dz[i][c] = (softmax(z_i)[c] - [c == y_i]) / N
+//   loss = mean_i( logsumexp(z_i) - z_i[y_i] ),   dz[i][c] = (softmax(z_i)[c] - [c == y_i]) / N   (at c == y_i: -(sum of the other classes' exp) / sum / N)
+// with logsumexp(z) - z[y] evaluated as (m - z[y]) + log1p(sum_{c != a} exp(z[c] - m)), m = z[a] the row maximum (a its first column):
+// -log(softmax[y]) saturates near 103 once exp(z[y] - m) underflows, and m + log(sum) - z[y] cancels on a confident row, where the
+// loss is far below one ulp of m.  A target on a class masked with -inf gives +inf, as F.cross_entropy does.
 // torch's generic nll_loss kernels need 0.75 ms for 5*10^5 x 8 logits; this streams them once (~20 MB).
 namespace pp {
 
@@ -1726,31 +1729,30 @@ __global__ __launch_bounds__(kBlock) void k_cross_entropy(const float* __restric
     float local = 0.f;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const int64_t y = target[i];
         float z[kMaxC];
-        float m = -INFINITY;
+        float m = -INFINITY, zy = -INFINITY;
+        int am = 0;
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c) {
             z[c] = c < C ? logits[i * C + c] : -INFINITY;
-            m = z[c] > m ? z[c] : m;
+            if (c == y) zy = z[c];
+            if (z[c] > m) { m = z[c]; am = c; }
         }
-        float sum = 0.f;
+        float sum = 0.f, rest = 0.f, others = 0.f;            // all classes; all but the maximum's; all but the target's
 #pragma unroll
         for (int c = 0; c < kMaxC; ++c) {
             z[c] = c < C ? expf(z[c] - m) : 0.f;
             sum += z[c];
+            rest += c == am ? 0.f : z[c];
+            others += c == y ? 0.f : z[c];
         }
-        const int64_t y = target[i];
         const float inv = 1.f / sum;
-        float zy = 0.f;
 #pragma unroll
-        for (int c = 0; c < kMaxC; ++c) {
-            if (c < C) {
-                const float p = z[c] * inv;
-                if (c == y) zy = p;
-                if (dlogits) dlogits[i * C + c] = (p - (c == y ? 1.f : 0.f)) * inv_n;
-            }
+        for (int c = 0; c < kMaxC; ++c) {          // softmax[y] - 1 = -(sum of the others) / sum: no cancellation where softmax[y] is 1 - 1e-4
+            if (c < C && dlogits) dlogits[i * C + c] = (c == y ? -others : z[c]) * inv * inv_n;
         }
-        local += -logf(zy > 0.f ? zy : 1e-45f);
+        local += (m - zy) + log1pf(rest);
     }
     local = wave_sum(local);
     if (lane_id() == 0) s_part[wave_id()] = local;
@@ -1816,6 +1818,8 @@ int pp_cross_entropy_f32(const float* logits, const int64_t* target, int64_t n, 
 // few dozen host-side device queries: on a small graph or a per-rank share the optimizer's host time was 1 ms of a 3.3 ms step).
 // Same update as torch.optim.Adam (amsgrad off, maximize off):  g' = g + wd*p;  m += (1-b1)(g'-m);  v = b2 v + (1-b2) g'^2;
 // p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps).   blockIdx.y = tensor, blockIdx.x strides over its elements.
+// b1c = 1 - b1 and b2c = 1 - b2 are formed in double on the host and rounded once, as torch passes them: 1.f - 0.999f is 1.3e-5 relative
+// away from 0.001, with one sign on every step.
 namespace pp {
 constexpr int kAdamTensors = 24;                                  // tensors per launch (the table travels as a kernel argument)
 struct AdamTable {
@@ -1825,7 +1829,7 @@ struct AdamTable {
     float* v[kAdamTensors];
     int64_t n[kAdamTensors];
 };
-__global__ __launch_bounds__(kBlock) void k_adam(AdamTable t, float lr_over_bc1, float inv_sqrt_bc2, float b1, float b2, float eps, float wd) {
+__global__ __launch_bounds__(kBlock) void k_adam(AdamTable t, float lr_over_bc1, float inv_sqrt_bc2, float b1c, float b2, float b2c, float eps, float wd) {
     const int k = blockIdx.y;
     const int64_t n = t.n[k];
     float* __restrict__ p = t.p[k];
@@ -1835,8 +1839,8 @@ __global__ __launch_bounds__(kBlock) void k_adam(AdamTable t, float lr_over_bc1,
     for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += (int64_t)gridDim.x * kBlock) {
         const float pe = p[e];
         const float ge = g[e] + wd * pe;
-        const float me = m[e] + (1.f - b1) * (ge - m[e]);
-        const float ve = b2 * v[e] + (1.f - b2) * ge * ge;
+        const float me = m[e] + b1c * (ge - m[e]);
+        const float ve = b2 * v[e] + b2c * ge * ge;
         m[e] = me;
         v[e] = ve;
         p[e] = pe - lr_over_bc1 * (me / (sqrtf(ve) * inv_sqrt_bc2 + eps));
@@ -1875,8 +1879,8 @@ int pp_adam_f32(int n_tensors, void* const* params, const void* const* grads, vo
         for (int q = cnt; q < pp::kAdamTensors; ++q) { t.p[q] = nullptr; t.g[q] = nullptr; t.m[q] = nullptr; t.v[q] = nullptr; t.n[q] = 0; }
         int64_t gx = pp::ceil_div(longest, pp::kBlock);
         if (gx > 1024) gx = 1024;
-        pp::k_adam<<<dim3((unsigned)gx, (unsigned)cnt), pp::kBlock, 0, st>>>(t, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)beta1, (float)beta2,
-                                                                             (float)eps, (float)weight_decay);
+        pp::k_adam<<<dim3((unsigned)gx, (unsigned)cnt), pp::kBlock, 0, st>>>(t, (float)(lr / bc1), (float)(1.0 / sqrt(bc2)), (float)(1.0 - beta1), (float)beta2,
+                                                                             (float)(1.0 - beta2), (float)eps, (float)weight_decay);
         PP_LAUNCH_CHECK();
     }
     return PP_OK;

@@ -355,3 +355,48 @@ def test_small_grid_cases_are_exact_in_fp32():
         assert all(value.abs().max() > 0 for outputs in case.exact.values() for value, _, _ in outputs.values()), case_id
         built += 1
     assert built > 600
+
+
+def test_value_cases_are_exact_in_front_of_the_epilogue():
+    """Every builder of tests/test_gpu_value_domain.py, run here without a GPU: what stands in front of the ELU / ELU' epilogue, evaluated by
+    torch on the CPU in fp32 and in float64, is the same numbers (each sum has one non-zero term: a grid value, times a power of two on the
+    gradient side), and every grid value stands in every column.  The cross-entropy reference of the same module (``F.cross_entropy`` on float64
+    logits) agrees with the formula written out, its Adam reference with a float64 ``torch.optim.Adam``."""
+    import torch.nn.functional as F
+    from tests import value_cases as vc
+    x, want = vc.ELU_GRID
+    assert x.dtype == torch.float32 and want.dtype == torch.float64 and torch.equal(want, torch.where(x > 0, x.double(), torch.expm1(x.double())))
+    for lo, hi in ((-0.25, 0.0), (-100.0, -0.25), (0.0, 100.0)):                      # every branch of elu_fast, and the ends of each
+        assert bool(((x > lo) & (x < hi)).any()) and bool((x == lo).any()) and bool((x == hi).any())
+    assert int((x == 0).sum()) == 2 and bool(torch.signbit(x[x == 0]).any()) and not bool(torch.signbit(x[x == 0]).all())
+    act = vc.ACT_GRID
+    for value in (-1.0, -1.0 + 2.0 ** -24, 0.0, vc.TINY):
+        assert bool((act == value).any()), value
+    assert bool((act >= -1).all()) and bool(torch.signbit(act[act == 0]).any())
+    built = 0
+    for case_id, build, everywhere in vc.all_cases():
+        case = build()
+        f32, f64 = case.front(torch.float32), case.front(torch.float64)
+        assert f32.dtype == torch.float32 and torch.equal(f32.double(), f64) and torch.equal(f32, case.pre), case_id
+        if everywhere:
+            assert vc.covers(getattr(case, "act", case.pre), case.grid), case_id
+        built += 1
+    assert built > 40
+    for kind in vc.CE_KINDS:
+        for c in vc.CE_CLASSES:
+            z, y = vc.cross_entropy_case(kind, 1000, c)
+            (loss, grad), (plain, plain_grad) = vc.cross_entropy_reference(z, y), vc.cross_entropy_plain(z, y)
+            assert bool(torch.isinf(loss)) == (kind == "masked_target") and bool(torch.isfinite(grad).all()), (kind, c)
+            torch.testing.assert_close(loss, plain, rtol=1e-7 if kind == "margin20" else 1e-11, atol=0.0)
+            torch.testing.assert_close(grad, plain_grad, rtol=1e-11, atol=1e-18)
+            if kind.startswith("masked"):
+                assert bool((grad[torch.isinf(z) & (F.one_hot(y, c) == 0)] == 0).all()), (kind, c)
+    init, grads = vc.adam_inputs()
+    params = [torch.nn.Parameter(t.double().clone()) for t in init]
+    opt = torch.optim.Adam(params, **vc.ADAM)
+    for gs in grads:
+        for p, g in zip(params, gs):
+            p.grad = g.double()
+        opt.step()
+    for p, mine in zip(params, vc.adam_reference(init, grads, **vc.ADAM)):
+        torch.testing.assert_close(mine, p.detach(), rtol=1e-12, atol=1e-14)
