@@ -255,6 +255,37 @@ int pp_multiorder_prepare_range(const int64_t* edge_index, int64_t m, int64_t nu
                                 int32_t* ibase, int32_t* tlast, float* w, int32_t* rowptr, void* ws, size_t ws_bytes, pp_stream_t stream);
 int pp_multiorder_stitch(const int32_t* gathered, int64_t stride, int64_t last_at, int world, const int64_t* row_lo, const int64_t* edge_lo,
                          int32_t* cand_ptr, int32_t* cand_last, pp_stream_t stream);
+/* The same layers of OBSERVED WALKS: MultiOrderModel.from_path_data(paths, max_order >= 2, mode="propagation"),
+ * src/pathpyG/core/multi_order_model.py:194-241, on the walk store of PathData.append_walks, src/pathpyG/core/path_data.py:126-159:
+ * node_sequence [positions] int64 the first-order node of every walk position, dag_num_nodes [walks] int64 positions per walk (L_w >= 1),
+ * dag_weight [walks] float32, edge_index [2, m] int64 the chain (p, p + 1) of the positions of every walk, m = positions - walks.
+ * A position p of walk w(p) that is not its walk's last starts edge e = p - w(p) from node[p] to node[p + 1]; edge e continues into edge
+ * e + 1 iff p + 1 is not the last position of its walk either.
+ *
+ * pp_multiorder_prepare_paths: level 1, the outputs of pp_multiorder_prepare (same capacities with m edges for m events; `tab` [m] is indexed
+ *   by the edge id: {dst(e), e + 1, continues, e}), ready for pp_multiorder_step; the weight of an instance is its walk's dag_weight
+ *   (lift_order_edge_index_weighted with aggr="src"), instances of a node pair in position order (one stable radix sort by (source, target)).
+ *   edge_walk [m] int32: the walk of every edge (pp_multiorder_paths_inverse reads it).  ws: pp_multiorder_paths_ws_bytes(positions, walks,
+ *   num_nodes); pp_multiorder_result_ptr(ws) = {types, status, instances of level 2, long runs}.  The walk store is verified on the device:
+ *   status bit 3: the distinct node ids are not exactly 0 .. num_nodes - 1 (layer 1 of a path model uses the ids as given, lift_order.py:135-136;
+ *     only id == rank is taken);
+ *   status bit 5: edge_index is not the chain (p, p + 1) of these walks, some L_w < 1, or the L_w do not add up to `positions`;
+ *   bit 2 as pp_multiorder_prepare.  With bit 3 or 5 set the outputs are not to be used (nothing was written out of bounds): the caller takes the
+ *   generic kernels (pp_linegraph_*, pp_coalesce_*).
+ * pp_multiorder_paths_inverse: inverse_idx of layer level + 1 (level >= 1) — for every (level + 1)-gram of consecutive walk positions, in
+ *   start-position order (the reference's instance order), its node of layer level + 1 = its type at `level` — from that level while its
+ *   `inst` is alive: tptr [n_types + 1], inst [n_instances] as pp_multiorder_prepare_paths (level 1) or pp_multiorder_step (child, last == 0)
+ *   left them.  Instance i of type t ends with edge e = inst[i].x - 1, starts with f = e - (level - 1) and has the rank
+ *   f - sum over the walks w' before edge_walk[e] of min(L_w' - 1, level - 1).  inverse [n_instances] int32.  ws: pp_multiorder_paths_inverse_ws_bytes(walks).
+ * Known limit: a k-gram observed at more than 4096 walk positions that all continue is a type with more than 4096 children (status bit 2 of
+ *   pp_multiorder_step): the whole model goes to the generic kernels, as on dense contact streams. */
+size_t pp_multiorder_paths_ws_bytes(int64_t positions, int64_t walks, int64_t num_nodes);
+int pp_multiorder_prepare_paths(const int64_t* node_sequence, int64_t positions, const int64_t* dag_num_nodes, const float* dag_weight, int64_t walks,
+                                const int64_t* edge_index, int64_t m, int64_t num_nodes, void* tab, void* inst, int32_t* tptr, int32_t* ibase,
+                                int32_t* tlast, float* w, int32_t* rowptr, int32_t* edge_walk, void* ws, size_t ws_bytes, pp_stream_t stream);
+size_t pp_multiorder_paths_inverse_ws_bytes(int64_t walks);
+int pp_multiorder_paths_inverse(int64_t level, int64_t n_types, int64_t n_instances, const int32_t* tptr, const void* inst, const int32_t* edge_walk,
+                                int64_t m, const int64_t* dag_num_nodes, int64_t walks, int32_t* inverse, void* ws, size_t ws_bytes, pp_stream_t stream);
 
 /* ------------------------------------------------------------------ order lifts (pp_lift.hip) */
 

@@ -1008,6 +1008,81 @@ def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
     return layers
 
 
+def multi_order_paths(node_sequence: torch.Tensor, dag_num_nodes: torch.Tensor, dag_weight: torch.Tensor, edge_index: torch.Tensor, num_nodes: int,
+                      max_order: int, want_inverse=True, clock: list | None = None):
+    """All De Bruijn layers 1..max_order of OBSERVED WALKS (``PathData``'s tensors: ``node_sequence`` [P] or [P, 1] int64, ``dag_num_nodes`` [W]
+    int64, ``dag_weight`` [W] float32, ``edge_index`` [2, P - W] int64; propagation mode), level by level: pp_multiorder_prepare_paths makes
+    level 1 straight from the walk store, the unchanged pp_multiorder_step every further one, pp_multiorder_paths_inverse the ``inverse_idx`` of a
+    layer from the level below it while that level's instances are alive.  ``num_nodes``: 1 + the largest node id.  Returns ``(layers,
+    inverses)``: ``[MultiOrderLayer]`` as :func:`multi_order_temporal` and ``{k: int32 [instances of level k - 1]}`` for the layers k >= 2
+    (``want_inverse``: True = all, "top" = layer ``max_order`` only, False = none) — or ``None`` when the generic kernels have to take over: node
+    ids that are not exactly 0 .. num_nodes - 1, an ``edge_index`` that is not the chain of these walks (status bits 3 / 5), a layer without
+    edges below ``max_order``, a node sequence observed at more than 4096 walk positions that all continue, 2^31 or more instances.
+    ``clock`` receives ``(name, start event, end event)`` for "prepare", every "layer k" and every "inverse k"."""
+    ei = _edge_index(edge_index)
+    seq = node_sequence.reshape(-1).contiguous()
+    lengths, weight = dag_num_nodes.contiguous(), dag_weight.contiguous()
+    dev = require_device(ei, seq, lengths, weight)
+    if seq.dtype != torch.int64 or lengths.dtype != torch.int64 or weight.dtype != torch.float32:
+        raise TypeError("multi_order_paths: node_sequence / dag_num_nodes int64 and dag_weight float32 expected")
+    positions, walks, m, n = seq.numel(), lengths.numel(), ei.size(1), int(num_nodes)
+    if m == 0 or n <= 0 or walks == 0 or weight.numel() != walks or m != positions - walks or positions >= _INT32_ROWS or n >= 1 << 31:
+        return None
+
+    def tick():
+        if clock is None:
+            return None
+        ev = torch.cuda.Event(enable_timing=True)
+        ev.record()
+        return ev
+    L = lib()
+    with torch.cuda.device(dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        t0 = tick()
+        tab, inst = torch.empty((m, 4), **i32), torch.empty((m, 4), **i32)
+        tptr, ibase = torch.empty(m + 1, **i32), torch.empty(m + 1, **i32)
+        tlast, w, edge_walk = torch.empty(m, **i32), torch.empty(m, **f32), torch.empty(m, **i32)
+        row_ptr = torch.empty(n + 1, **i32)
+        ws = _workspace(L.pp_multiorder_paths_ws_bytes(positions, walks, n), dev)
+        check(L.pp_multiorder_prepare_paths(_p(seq), positions, _p(lengths), _p(weight), walks, _p(ei), m, n, _p(tab), _p(inst), _p(tptr), _p(ibase),
+                                            _p(tlast), _p(w), _p(row_ptr), _p(edge_walk), _p(ws), ws.numel(), _stream()), "pp_multiorder_prepare_paths")
+        types, status, children, _ = ws[:32].view(torch.int64).tolist()
+        if clock is not None:
+            clock.append(("prepare", t0, tick()))
+        del ws
+        if status & (8 | 32 | 4 | 16):
+            return None                  # (ids with gaps or a foreign edge_index: the generic route; 2^31 continuations)
+        level = MultiOrderLevel(types=types, children=children, status=status, tptr=tptr, ibase=ibase, inst=inst, row_ptr=row_ptr, col=tlast,
+                                weight=w, tlast=tlast)
+        layers = [MultiOrderLayer(n_nodes=n, n_edges=types, n_instances=m, row_ptr=row_ptr, col=tlast[:types], weight=w[:types], last=tlast[:types])]
+        inverses = {}
+        cand_ptr, cand_last = row_ptr, tlast
+        instances = m
+        inv_ws = _workspace(L.pp_multiorder_paths_inverse_ws_bytes(walks), dev) if want_inverse else None
+        for k in range(2, max_order + 1):
+            if level.types == 0 or level.children == 0 or level.children >= _INT32_ROWS:
+                return None
+            if want_inverse is True or (want_inverse == "top" and k == max_order):
+                t0 = tick()
+                inverse = torch.empty(instances, **i32)
+                check(L.pp_multiorder_paths_inverse(k - 1, level.types, instances, _p(level.tptr), _p(level.inst), _p(edge_walk), m, _p(lengths), walks,
+                                                    _p(inverse), _p(inv_ws), inv_ws.numel(), _stream()), "pp_multiorder_paths_inverse")
+                inverses[k] = inverse
+                if clock is not None:
+                    clock.append((f"inverse {k}", t0, tick()))
+            last = k == max_order
+            nxt = _multi_order_step(level, cand_ptr, cand_last, tab, True, last, clock, f"layer {k}")
+            if nxt.status & 4:
+                return None
+            layers.append(MultiOrderLayer(n_nodes=level.types, n_edges=nxt.types, n_instances=level.children, row_ptr=nxt.row_ptr, col=nxt.col[:nxt.types],
+                                          weight=nxt.weight[:nxt.types], last=None if last else nxt.tlast[:nxt.types]))
+            cand_ptr, cand_last = nxt.row_ptr, nxt.tlast
+            instances = level.children
+            level = nxt
+    return layers, inverses
+
+
 class MultiOrderLevel:
     """Level k of the level-by-level builder on the device, with layer k as it left the kernels: ``types`` types (= edges of layer k) with
     ``children`` instances at level k + 1 (both on the host, with ``status``, from the level's one read-back); ``tptr`` / ``ibase`` [types + 1],

@@ -149,7 +149,15 @@ class MultiOrderModel:
     @staticmethod
     def from_path_data(path_data: PathData, max_order: int = 1, mode: str = "propagation", cached: bool = True) -> "MultiOrderModel":
         """De Bruijn layers of observed walks (reference multi_order_model.py:194-241).
-        ``mode="propagation"`` carries the walk weight along; ``"diffusion"`` splits it by out-degree."""
+        ``mode="propagation"`` carries the walk weight along; ``"diffusion"`` splits it by out-degree.
+
+        Propagation mode with ``max_order >= 2`` on a device-resident walk store builds the layers level by level (:func:`_paths_fused`);
+        everything else — diffusion, host-resident walks, another weight dtype, ``max_order == 1``, node ids with gaps, a node sequence
+        observed at more than 4096 walk positions that all continue — runs on the generic kernels below.  Same layers either way."""
+        if max_order >= 2 and mode == "propagation" and FUSED_BUILDER:
+            fused = _paths_fused(path_data, max_order, cached)
+            if fused is not None:
+                return fused
         m = MultiOrderModel()
         walks = path_data.data
         edge_index = walks.edge_index
@@ -456,6 +464,68 @@ def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, wei
             if k == 2:
                 layers[k]._nodes_are_fo_edges = True
     return layers
+
+
+def _path_csr_layers(mapping: IndexMap, node_sequence: torch.Tensor, csr: list, inverses: dict, cached: bool, gather_concat=None) -> dict:
+    """:func:`_csr_layers` for a model of observed walks (reference multi_order_model.py:211-241): the layers a level-by-level build of a walk
+    store keeps — layer 1 always (the reference keeps it whatever ``cached`` says), with ``cached=False`` otherwise only the top one — as
+    :class:`~pathpyg_amd.data.Lazy` views of the CSR arrays ``csr[k - 1]`` = layer k.  The walks' node ids are 0 .. n - 1 without gaps (the
+    builder's precondition), so layer 1's ``node_sequence`` is ``arange(n)`` and its ``inverse_idx`` the walk store's ``node_sequence[:, 0]``;
+    ``inverses[k]``: the int32 ``inverse_idx`` of layer k >= 2 as pp_multiorder_paths_inverse left it, widened to int64 when read.  Mappings:
+    ``mapping`` for layer 1, ``IndexMap.from_node_sequence(mapping, node sequence of the layer)`` above.  ``gather_concat`` as in
+    :func:`_csr_layers`."""
+    gather_concat = _dispatch.gather_concat if gather_concat is None else gather_concat
+    n, dev = csr[0].n_nodes, node_sequence.device
+    positions = node_sequence.size(0)
+    layers = {}
+    index = seq = None
+    for k, b in enumerate(csr, start=1):
+        prev_index, prev_seq = index, seq
+        index = Lazy(lambda b=b: torch.stack((_csr_rows(b.row_ptr, b.n_edges), b.col.long())), (2, b.n_edges))
+        if k == 1:
+            seq = Lazy(lambda: torch.arange(n, device=dev).unsqueeze(1), (n, 1))
+            inverse = Lazy(lambda: node_sequence[:, 0].clone(), (positions,))
+        else:
+            if k == 2:
+                seq = Lazy(lambda first=prev_index: first.resolve().t().contiguous(), (b.n_nodes, 2))
+            else:
+                def seq_of(prev_index=prev_index, prev_seq=prev_seq, last=csr[k - 2].last):
+                    # node u of layer k = edge u of layer k-1: the sequence of that edge's source node, then the edge's last node
+                    return gather_concat(prev_seq.resolve(), prev_index.resolve()[0].contiguous(), last.long())
+
+                seq = Lazy(seq_of, (b.n_nodes, k))
+            inv32 = inverses.get(k)
+            inverse = None if inv32 is None else Lazy(lambda inv32=inv32: inv32.long(), (inv32.numel(),))
+        if cached or k == 1 or k == len(csr):
+            d = Data(edge_index=index, num_nodes=b.n_nodes, node_sequence=seq, edge_weight=b.weight, inverse_idx=inverse)
+            layers[k] = Graph._from_parts(d, mapping if k == 1 else IndexMap.from_node_sequence(mapping, seq))
+    return layers
+
+
+def _paths_fused(path_data: PathData, max_order: int, cached: bool):
+    """``from_path_data(paths, max_order >= 2, mode="propagation")`` level by level (``_hip.multi_order_paths`` -> ``pp_multiorder_prepare_paths``,
+    ``pp_multiorder_step``, ``pp_multiorder_paths_inverse``): no ``[2, E_k]`` instance graphs, one global sort (level 1), every layer's
+    ``inverse_idx`` from its closed form on the walks.  ``None``: the builder does not apply — walk tensors not all on the device with their
+    stock dtypes (int64 / float32), no edges — or handed the model back (see ``_hip.multi_order_paths``)."""
+    walks = path_data.data
+    ei = _dispatch.plain(walks.edge_index)
+    seq, lengths, weight = walks.node_sequence, walks.dag_num_nodes, walks.dag_weight
+    for t, dtype in ((ei, torch.int64), (seq, torch.int64), (lengths, torch.int64), (walks.dag_num_edges, torch.int64), (weight, torch.float32)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            return None
+    if ei.dim() != 2 or ei.size(0) != 2 or ei.size(1) == 0 or seq.dim() != 2 or seq.size(1) != 1:
+        return None
+    lo, hi = _hip.minmax(seq)
+    if lo < 0:
+        return None
+    built = _hip.multi_order_paths(seq, lengths, weight, ei, hi + 1, max_order, want_inverse=True if cached else "top")
+    if built is None:
+        return None
+    csr, inverses = built
+    out = MultiOrderModel()
+    out.sizes = {"m": int(ei.size(1)), "N": hi + 1, "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in csr]}
+    out.layers = _path_csr_layers(path_data.mapping, seq, csr, inverses, cached)
+    return out
 
 
 def _second_order_fused(g: TemporalGraph, delta, weight: str, cached: bool):

@@ -1055,19 +1055,14 @@ static MoPrepWs carve_mo_prep(void* ws, int64_t m, int64_t m_ev) {
     return w;
 }
 
+// level 1 from the (source, target) keys of the events in their order (p.keys_a) and their records (p.ev): ONE stable sort by the key
 template <typename KeyT>
-static int mo_level1(const MoPrepWs& p, const TemporalLists& tl, const int64_t* src, const int64_t* dst, const float* weight, int64_t m,
-                     int64_t num_nodes, int bits, uint4* inst, int32_t* tptr, int32_t* tlast, int32_t* rowptr, hipStream_t st) {
+static int mo_level1_keyed(const MoPrepWs& p, int64_t m, int64_t num_nodes, int bits, uint4* inst, int32_t* tptr, int32_t* tlast, int32_t* rowptr,
+                           hipStream_t st) {
     const unsigned grid = (unsigned)ceil_div(m, kBlock);
-    KeyT* keys = (KeyT*)p.keys_a;
     KeyT* sorted = (KeyT*)p.keys_b;
-    // the events in (source, target, time) order: ONE stable sort of the time-ordered stream by the (source, target) key
-    k_mo_key_pair<KeyT><<<grid, kBlock, 0, st>>>(src, dst, m, num_nodes, bits, keys);
-    PP_LAUNCH_CHECK();
-    int rc = sort_pairs<KeyT>(keys, nullptr, sorted, p.perm, m, 0, 2 * bits, p.scratch, p.scratch_bytes, st);
+    int rc = sort_pairs<KeyT>((const KeyT*)p.keys_a, nullptr, sorted, p.perm, m, 0, 2 * bits, p.scratch, p.scratch_bytes, st);
     if (rc != PP_OK) return rc;
-    k_mo_events<<<grid, kBlock, 0, st>>>(dst, tl.first_pos, tl.count, weight, m, num_nodes, p.ev);
-    PP_LAUNCH_CHECK();
     k_mo_inst1<KeyT><<<grid, kBlock, 0, st>>>(sorted, p.perm, p.ev, m, inst, p.head);
     PP_LAUNCH_CHECK();
     rc = exclusive_scan<int32_t, int32_t>(p.head, m, p.head_before, true, p.result, p.scratch, p.scratch_bytes, st);
@@ -1075,6 +1070,18 @@ static int mo_level1(const MoPrepWs& p, const TemporalLists& tl, const int64_t* 
     k_mo_types1<KeyT><<<grid, kBlock, 0, st>>>(sorted, bits, p.head_before, m, num_nodes, tptr, tlast, rowptr);
     PP_LAUNCH_CHECK();
     return PP_OK;
+}
+
+template <typename KeyT>
+static int mo_level1(const MoPrepWs& p, const TemporalLists& tl, const int64_t* src, const int64_t* dst, const float* weight, int64_t m,
+                     int64_t num_nodes, int bits, uint4* inst, int32_t* tptr, int32_t* tlast, int32_t* rowptr, hipStream_t st) {
+    const unsigned grid = (unsigned)ceil_div(m, kBlock);
+    // the events in (source, target, time) order: ONE stable sort of the time-ordered stream by the (source, target) key
+    k_mo_key_pair<KeyT><<<grid, kBlock, 0, st>>>(src, dst, m, num_nodes, bits, (KeyT*)p.keys_a);
+    PP_LAUNCH_CHECK();
+    k_mo_events<<<grid, kBlock, 0, st>>>(dst, tl.first_pos, tl.count, weight, m, num_nodes, p.ev);
+    PP_LAUNCH_CHECK();
+    return mo_level1_keyed<KeyT>(p, m, num_nodes, bits, inst, tptr, tlast, rowptr, st);
 }
 
 // the same on a rank's own events: ONE stable sort of its list range (grouped by source, time order inside) by the (source, target) key
@@ -1095,6 +1102,18 @@ static int mo_level1_range(const MoPrepWs& p, const TemporalLists& tl, const int
     k_mo_types1<KeyT><<<grid, kBlock, 0, st>>>(sorted, bits, p.head_before, rg.m_own, rg.n_own, tptr, tlast, rowptr);
     PP_LAUNCH_CHECK();
     return PP_OK;
+}
+
+// merged weights and children counts of the level-1 types (p.csum zeroed, p.counters zeroed), then the first child of every type
+static int mo_level1_sums(const MoPrepWs& p, bool weighted, int64_t mo, const void* inst, const int32_t* tptr, int32_t* ibase, float* w, hipStream_t st) {
+    const unsigned grid = (unsigned)ceil_div(mo, kBlock);
+    if (weighted) k_mo_sums1<true><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
+    else k_mo_sums1<false><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
+    PP_LAUNCH_CHECK();
+    if (weighted) k_mo_sums1_long<true><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
+    else k_mo_sums1_long<false><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
+    PP_LAUNCH_CHECK();
+    return exclusive_scan<int32_t, int32_t>(p.csum, mo, ibase, true, p.result + 2, p.scratch, p.scratch_bytes, st);
 }
 
 struct MoStepWs {
@@ -1126,6 +1145,149 @@ __global__ void k_mo_finish(const int32_t* __restrict__ counters, const int64_t*
     if (lift_result) atomicOr((unsigned long long*)(result + 1), (unsigned long long)lift_result[1]);
 }
 
+// ------------------------------------------------------------------ level 1 from a walk store (MultiOrderModel.from_path_data)
+// Walks are the easiest input of this builder: the only continuation of walk edge e is edge e + 1 of the same walk.  With the positions of
+// all walks concatenated (PathData.append_walks), position p of walk w(p) that is not its walk's last starts edge e = p - w(p); `tab` is
+// indexed by the edge id itself: {dst(e), e + 1, continues ? 1 : 0, e} — no per-node lists, no windows pass, no gather.  The window first
+// e + 1 is written even for a count of 0: the children kernels copy a child's window from `tab` as it is, so at EVERY level the last edge
+// of an instance is inst.x - 1 (what pp_multiorder_paths_inverse reads).
+constexpr int64_t kMoPathIds = 8, kMoPathChain = 32;      // status bits 3 and 5 (0, 1, 2, 4 are taken: kMoBadIndex, kMoUnsorted, kMoOverflow, kMoLongList)
+
+// positions per walk as int32, 1 <= L <= positions (anything else: kMoPathChain, clamped so that nothing runs off an array)
+__global__ __launch_bounds__(kBlock) void k_mo_path_lengths(const int64_t* __restrict__ dag_num_nodes, int64_t walks, int64_t positions,
+                                                           int32_t* __restrict__ len, int64_t* __restrict__ status) {
+    const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (w >= walks) return;
+    int64_t l = dag_num_nodes[w];
+    if (l < 1 || l > positions) {
+        atomicOr((unsigned long long*)status, (unsigned long long)kMoPathChain);
+        l = l < 1 ? 0 : positions;
+    }
+    len[w] = (int32_t)l;
+}
+
+// flag of the first position of every walk (`start` zeroed); the lengths add up to the number of positions
+__global__ __launch_bounds__(kBlock) void k_mo_path_starts(const int64_t* __restrict__ pstart, int64_t walks, int64_t positions, int32_t* __restrict__ start,
+                                                          int64_t* __restrict__ status) {
+    const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (w >= walks) return;
+    const int64_t s = pstart[w];
+    if (s < positions) start[s] = 1;
+    if (w == 0 && pstart[walks] != positions) atomicOr((unsigned long long*)status, (unsigned long long)kMoPathChain);
+}
+
+// one thread per position: its node id is checked and marked present; a position that is not the last of its walk writes the record, the
+// table entry, the (source, target) sort key and the walk of its edge, and checks its column of edge_index (the chain (p, p + 1))
+template <typename KeyT>
+__global__ __launch_bounds__(kBlock) void k_mo_path_records(const int64_t* __restrict__ node, const int32_t* __restrict__ starts_before,
+                                                           const int64_t* __restrict__ pstart, const float* __restrict__ dag_weight,
+                                                           const int64_t* __restrict__ edge_index, int64_t positions, int64_t m, int64_t n, int bits,
+                                                           uint4* __restrict__ ev, uint4* __restrict__ tab, KeyT* __restrict__ keys,
+                                                           int32_t* __restrict__ edge_walk, int32_t* __restrict__ present, int64_t* __restrict__ status) {
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= positions) return;
+    int64_t a = node[p];
+    if (a < 0 || a >= n) { atomicOr((unsigned long long*)status, (unsigned long long)kMoPathIds); a = 0; }
+    present[a] = 1;
+    const int64_t w = (int64_t)starts_before[p + 1] - 1;       // walks that start at or before p, less one (position 0 starts walk 0)
+    const int64_t end = pstart[w + 1];
+    if (p + 1 >= end || p + 1 >= positions) return;             // the last position of its walk starts no edge
+    const int64_t e = p - w;
+    if (e >= m) { atomicOr((unsigned long long*)status, (unsigned long long)kMoPathChain); return; }
+    if (edge_index[e] != p || edge_index[m + e] != p + 1) atomicOr((unsigned long long*)status, (unsigned long long)kMoPathChain);
+    int64_t b = node[p + 1];
+    if (b < 0 || b >= n) b = 0;                                 // (its own thread sets the bit)
+    const uint32_t cont = p + 2 < end ? 1u : 0u;
+    ev[e] = make_uint4((uint32_t)b, (uint32_t)(e + 1), cont, __float_as_uint(dag_weight[w]));
+    tab[e] = make_uint4((uint32_t)b, (uint32_t)(e + 1), cont, (uint32_t)e);
+    keys[e] = ((KeyT)a << bits) | (KeyT)b;
+    edge_walk[e] = (int32_t)w;
+}
+
+// the distinct node ids are exactly 0 .. n - 1 (layer 1 of a path model uses the ids as given; only id == rank is taken)
+__global__ __launch_bounds__(kBlock) void k_mo_path_present(const int32_t* __restrict__ present, int64_t n, int64_t* __restrict__ status) {
+    const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (v < n && present[v] == 0) atomicOr((unsigned long long*)status, (unsigned long long)kMoPathIds);
+}
+
+struct MoPathWs {
+    MoPrepWs prep;            // (first: the result header sits at the start of the workspace)
+    int32_t *len, *start, *starts_before, *present;
+    int64_t* pstart;          // [walks + 1] first position of every walk
+    void* scratch;
+    size_t scratch_bytes, total_bytes;
+};
+static MoPathWs carve_mo_paths(void* ws, int64_t positions, int64_t walks, int64_t num_nodes) {
+    const int64_t m = positions > walks ? positions - walks : 1;
+    MoPathWs w;
+    w.prep = carve_mo_prep(ws, m, m);
+    Arena a(ws ? (char*)ws + w.prep.total_bytes : nullptr, (size_t)-1);
+    w.len = a.take<int32_t>(walks);
+    w.pstart = a.take<int64_t>(walks + 1);
+    w.start = a.take<int32_t>(positions);
+    w.starts_before = a.take<int32_t>(positions + 1);
+    w.present = a.take<int32_t>(num_nodes);
+    w.scratch_bytes = scan_ws_bytes(positions + 1);
+    w.scratch = a.take<char>((int64_t)w.scratch_bytes);
+    w.total_bytes = w.prep.total_bytes + a.used;
+    return w;
+}
+
+template <typename KeyT>
+static int mo_paths_level1(const MoPathWs& q, const int64_t* node, const float* dag_weight, const int64_t* edge_index, int64_t positions, int64_t m,
+                           int64_t num_nodes, int bits, uint4* tab, uint4* inst, int32_t* tptr, int32_t* tlast, int32_t* rowptr, int32_t* edge_walk,
+                           hipStream_t st) {
+    k_mo_path_records<KeyT><<<(unsigned)ceil_div(positions, kBlock), kBlock, 0, st>>>(node, q.starts_before, q.pstart, dag_weight, edge_index, positions, m,
+                                                                                      num_nodes, bits, q.prep.ev, tab, (KeyT*)q.prep.keys_a, edge_walk,
+                                                                                      q.present, q.prep.result + 1);
+    PP_LAUNCH_CHECK();
+    return mo_level1_keyed<KeyT>(q.prep, m, num_nodes, bits, inst, tptr, tlast, rowptr, st);
+}
+
+// ------------------------------------------------------------------ inverse_idx of a path model's layer j + 1 from level j
+// min(L_w - 1, j - 1): the edges of walk w that start no path of j edges inside it, but for those past its end
+__global__ __launch_bounds__(kBlock) void k_mo_path_skip(const int64_t* __restrict__ dag_num_nodes, int64_t walks, int64_t level, int32_t* __restrict__ out) {
+    const int64_t w = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (w >= walks) return;
+    int64_t l = dag_num_nodes[w] - 1;
+    l = l < 0 ? 0 : l;
+    out[w] = (int32_t)(l < level - 1 ? l : level - 1);
+}
+
+// One thread per instance i of level j: its type t by bisection in tptr (a type with thousands of instances costs every lane the same),
+// its last edge e = inst.x - 1, first edge f = e - (j - 1), rank among the reference's instances r = f - skip_j[walk of e].
+__global__ __launch_bounds__(kBlock) void k_mo_path_inverse(const int32_t* __restrict__ tptr, int64_t n_types, const uint4* __restrict__ inst,
+                                                           int64_t n_inst, const int32_t* __restrict__ edge_walk, int64_t m,
+                                                           const int32_t* __restrict__ skip, int64_t level, int32_t* __restrict__ inverse) {
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_inst) return;
+    int64_t lo = 0, hi = n_types;                  // last type whose range starts at or before i (no type is empty)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if ((int64_t)tptr[mid] <= i) lo = mid; else hi = mid;
+    }
+    const int64_t e = (int64_t)inst[i].x - 1;
+    if (e < 0 || e >= m) return;                    // (cannot happen for the levels of pp_multiorder_prepare_paths; nothing may run off an array)
+    const int64_t r = e - (level - 1) - (skip ? (int64_t)skip[edge_walk[e]] : 0);
+    if (r >= 0 && r < n_inst) inverse[r] = (int32_t)lo;
+}
+
+struct MoPathInvWs {
+    int32_t *vals, *skip;
+    void* scratch;
+    size_t scratch_bytes, total_bytes;
+};
+static MoPathInvWs carve_mo_path_inv(void* ws, int64_t walks) {
+    Arena a(ws, (size_t)-1);
+    MoPathInvWs w;
+    w.vals = a.take<int32_t>(walks);
+    w.skip = a.take<int32_t>(walks + 1);
+    w.scratch_bytes = scan_ws_bytes(walks + 1);
+    w.scratch = a.take<char>((int64_t)w.scratch_bytes);
+    w.total_bytes = a.used;
+    return w;
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -1150,7 +1312,6 @@ static int mo_prepare(const int64_t* edge_index, int64_t m, int64_t num_nodes, c
     PP_HIP(hipMemsetAsync(p.csum, 0, (size_t)mo * sizeof(int32_t), st));
     const int64_t* src = edge_index;
     const int64_t* dst = edge_index + m;
-    const unsigned grid = (unsigned)ceil_div(mo, kBlock);
     const int bits = bits_for((uint64_t)(num_nodes - 1));
     int rc;
     bool tab_done = false;               // (the list kernels write the window table on their way)
@@ -1186,13 +1347,7 @@ static int mo_prepare(const int64_t* edge_index, int64_t m, int64_t num_nodes, c
                             : mo_level1<uint64_t>(p, tl, src, dst, weight, m, num_nodes, bits, (uint4*)inst, tptr, tlast, rowptr, st);
         if (rc != PP_OK) return rc;
     }
-    if (weight) k_mo_sums1<true><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
-    else k_mo_sums1<false><<<grid, kBlock, 0, st>>>(tptr, p.head_before + mo, (const uint4*)inst, w, p.csum, p.long_list, p.counters, p.result + 1);
-    PP_LAUNCH_CHECK();
-    if (weight) k_mo_sums1_long<true><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
-    else k_mo_sums1_long<false><<<256, kBlock, 0, st>>>(tptr, (const uint4*)inst, p.long_list, p.counters, w, p.csum, p.result + 1);
-    PP_LAUNCH_CHECK();
-    rc = exclusive_scan<int32_t, int32_t>(p.csum, mo, ibase, true, p.result + 2, p.scratch, p.scratch_bytes, st);
+    rc = mo_level1_sums(p, weight != nullptr, mo, inst, tptr, ibase, w, st);
     if (rc != PP_OK) return rc;
     if (n_list > 0 && !tab_done) k_mo_tab<<<(unsigned)ceil_div(n_list, kBlock), kBlock, 0, st>>>(tl.ids, p.ev, n_list, (uint4*)tab);
     PP_LAUNCH_CHECK();
@@ -1351,6 +1506,77 @@ int pp_multiorder_step(int64_t n_types, int64_t n_children, const int32_t* tptr,
         if (rc != PP_OK) return rc;
     }
     k_mo_finish<<<1, 1, 0, st>>>(p.counters, nullptr, p.result);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+/* see include/pathpyg_amd.h: level 1 from a walk store */
+size_t pp_multiorder_paths_ws_bytes(int64_t positions, int64_t walks, int64_t num_nodes) { return carve_mo_paths(nullptr, positions, walks, num_nodes).total_bytes; }
+
+int pp_multiorder_prepare_paths(const int64_t* node_sequence, int64_t positions, const int64_t* dag_num_nodes, const float* dag_weight, int64_t walks,
+                                const int64_t* edge_index, int64_t m, int64_t num_nodes, void* tab, void* inst, int32_t* tptr, int32_t* ibase,
+                                int32_t* tlast, float* w, int32_t* rowptr, int32_t* edge_walk, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(m > 0 && walks > 0 && num_nodes > 0, PP_ERR_ARG, "pp_multiorder_prepare_paths: no walks, no edges or no nodes");
+    PP_REQUIRE(m == positions - walks, PP_ERR_ARG, "pp_multiorder_prepare_paths: %lld edges for %lld positions of %lld walks", (long long)m,
+               (long long)positions, (long long)walks);
+    PP_REQUIRE(positions < (int64_t)0x7ffffff0 && num_nodes < ((int64_t)1 << 31), PP_ERR_TOO_LARGE, "pp_multiorder_prepare_paths: positions or num_nodes >= 2^31");
+    MoPathWs q = carve_mo_paths(ws, positions, walks, num_nodes);
+    PP_REQUIRE(ws_bytes >= q.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_prepare_paths: workspace too small");
+    const MoPrepWs& p = q.prep;
+    PP_HIP(hipMemsetAsync(p.result, 0, 4 * sizeof(int64_t), st));
+    PP_HIP(hipMemsetAsync(p.counters, 0, 4 * sizeof(int32_t), st));
+    PP_HIP(hipMemsetAsync(p.csum, 0, (size_t)m * sizeof(int32_t), st));
+    PP_HIP(hipMemsetAsync(q.start, 0, (size_t)positions * sizeof(int32_t), st));
+    PP_HIP(hipMemsetAsync(q.present, 0, (size_t)num_nodes * sizeof(int32_t), st));
+    // (an edge that inconsistent walk lengths leave unwritten sorts as the pair (0, 0) with no continuation: the status bit is set, nothing runs off an array)
+    PP_HIP(hipMemsetAsync(p.keys_a, 0, (size_t)m * sizeof(uint64_t), st));
+    PP_HIP(hipMemsetAsync(p.ev, 0, (size_t)m * sizeof(uint4), st));
+    const unsigned wgrid = (unsigned)ceil_div(walks, kBlock);
+    k_mo_path_lengths<<<wgrid, kBlock, 0, st>>>(dag_num_nodes, walks, positions, q.len, p.result + 1);
+    PP_LAUNCH_CHECK();
+    int rc = exclusive_scan<int32_t, int64_t>(q.len, walks, q.pstart, true, nullptr, q.scratch, q.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_mo_path_starts<<<wgrid, kBlock, 0, st>>>(q.pstart, walks, positions, q.start, p.result + 1);
+    PP_LAUNCH_CHECK();
+    rc = exclusive_scan<int32_t, int32_t>(q.start, positions, q.starts_before, true, nullptr, q.scratch, q.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    const int bits = bits_for((uint64_t)(num_nodes - 1));
+    rc = 2 * bits <= 32 ? mo_paths_level1<uint32_t>(q, node_sequence, dag_weight, edge_index, positions, m, num_nodes, bits, (uint4*)tab, (uint4*)inst, tptr,
+                                                    tlast, rowptr, edge_walk, st)
+                        : mo_paths_level1<uint64_t>(q, node_sequence, dag_weight, edge_index, positions, m, num_nodes, bits, (uint4*)tab, (uint4*)inst, tptr,
+                                                    tlast, rowptr, edge_walk, st);
+    if (rc != PP_OK) return rc;
+    k_mo_path_present<<<(unsigned)ceil_div(num_nodes, kBlock), kBlock, 0, st>>>(q.present, num_nodes, p.result + 1);
+    PP_LAUNCH_CHECK();
+    rc = mo_level1_sums(p, true, m, inst, tptr, ibase, w, st);
+    if (rc != PP_OK) return rc;
+    k_mo_finish<<<1, 1, 0, st>>>(p.counters, nullptr, p.result);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+/* see include/pathpyg_amd.h: inverse_idx of layer `level` + 1 of a path model */
+size_t pp_multiorder_paths_inverse_ws_bytes(int64_t walks) { return carve_mo_path_inv(nullptr, walks).total_bytes; }
+
+int pp_multiorder_paths_inverse(int64_t level, int64_t n_types, int64_t n_instances, const int32_t* tptr, const void* inst, const int32_t* edge_walk,
+                                int64_t m, const int64_t* dag_num_nodes, int64_t walks, int32_t* inverse, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(level >= 1 && n_types > 0 && n_instances > 0 && m > 0 && walks > 0, PP_ERR_ARG, "pp_multiorder_paths_inverse: empty level");
+    PP_REQUIRE(n_instances < (int64_t)0x7ffffff0 && m < (int64_t)0x7ffffff0 && level < (int64_t)0x7ffffff0, PP_ERR_TOO_LARGE,
+               "pp_multiorder_paths_inverse: level with 2^31 or more instances");
+    MoPathInvWs q = carve_mo_path_inv(ws, walks);
+    PP_REQUIRE(ws_bytes >= q.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_paths_inverse: workspace too small");
+    const int32_t* skip = nullptr;                  // (level 1: every edge is an instance, rank = edge id)
+    if (level > 1) {
+        k_mo_path_skip<<<(unsigned)ceil_div(walks, kBlock), kBlock, 0, st>>>(dag_num_nodes, walks, level, q.vals);
+        PP_LAUNCH_CHECK();
+        const int rc = exclusive_scan<int32_t, int32_t>(q.vals, walks, q.skip, true, nullptr, q.scratch, q.scratch_bytes, st);
+        if (rc != PP_OK) return rc;
+        skip = q.skip;
+    }
+    k_mo_path_inverse<<<(unsigned)ceil_div(n_instances, kBlock), kBlock, 0, st>>>(tptr, n_types, (const uint4*)inst, n_instances, edge_walk, m, skip, level,
+                                                                                  inverse);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
