@@ -674,6 +674,51 @@ int pp_temporal_betweenness(const int64_t* edge_index, int64_t m, int64_t n, con
                             const int64_t* by_src_ptr, const int64_t* by_src, const int64_t* by_dst_ptr, const int64_t* by_dst,
                             double* partial, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ order selection (pp_selection.hip) */
+
+/* Index arrays below are int32 (`*_wide` = 0) or int64 (1): the level-by-level builders keep int32 CSR arrays, Graph.row_ptr is int64.
+ * Status words (int64, 0 = fine): bit 0 an index outside its range (it was not read), bit 1 a row pointer array that is not ascending
+ * from 0 to the entry count, bit 2 a node id in [0, n) that never occurs, bit 3 walk lengths that do not fit the store.
+ *
+ * pp_walk_counts_i64: the path counts of MultiOrderModel.get_mon_dof(assumption="paths"), src/pathpyG/core/multi_order_model.py:283-309,
+ * without the k-1 line-graph lifts of :283-291 (lift_order_edge_index, lift_order.py:47-81) and without the sparse matrix power of
+ * :293-309 — and the answer to the "TODO: can it be done together?" there: c_1[v] = out-degree(v), c_k[v] = sum of c_{k-1} over the
+ * successors of v, pushed K times through the source-major CSR (row_ptr [n+1], col [n_edges]).
+ *   out [3K + 1] int64: totals[k-1] = sum_v c_k[v] (walks of length k), starts[k-1] = #{v : c_k[v] > 0} (rows of the order-k transition
+ *   matrix), saturated[k-1] = 1 when an addition of order k left int64 — every addition saturates at INT64_MAX, starts stay exact —
+ *   and the status word.  Rows of more than 1024 entries are summed by a workgroup; the totals are integer sums (two 64-bit words, one atomic
+ *   per workgroup and word): exact in any order.  ws: pp_walk_counts_ws_bytes(n, n_edges, K). */
+size_t pp_walk_counts_ws_bytes(int64_t n, int64_t n_edges, int64_t K);
+int pp_walk_counts_i64(const void* row_ptr, int ptr_wide, const void* col, int col_wide, int64_t n, int64_t n_edges, int64_t K, int64_t* out,
+                       void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* Two likelihood terms of one layer, from its source-major CSR (row_ptr [n_rows+1], weight [n_edges] float32), in float64:
+ *   out2[0] = T = sum_e w_e log(w_e / S_row(e)), S the float64 sum of the row's weights: the top-order term of
+ *     MultiOrderModel.get_mon_log_likelihood, multi_order_model.py:394-397 (Graph.transition_probabilities(edge_attr="edge_weight"),
+ *     src/pathpyG/core/graph.py:518-533);
+ *   out2[1] = I = sum_s freq_s log(1 / d(row of edge sel_s)), d the UNWEIGHTED out-degree: get_intermediate_order_log_likelihood,
+ *     multi_order_model.py:338-369 (:363 calls transition_probabilities() without edge_attr), sel [n_sel] the layer's edge of the first
+ *     transition of every surviving walk, freq [n_sel] float32 the walk weights; n_sel = 0: I = 0.  The row of an edge is found by
+ *     binary search in row_ptr.
+ * Both are pure functions of the input VALUES: fixed summation shapes (a row by 64 strided lanes, by 256 above 1024 entries; vectors
+ * by chunks of 2048 whose partial sums one workgroup adds in index order), no floating-point atomics; zero and negative weights
+ * follow IEEE arithmetic.  ws: pp_mon_layer_llh_ws_bytes(n_rows, n_edges, n_sel). */
+size_t pp_mon_layer_llh_ws_bytes(int64_t n_rows, int64_t n_edges, int64_t n_sel);
+int pp_mon_layer_llh_f64(const void* row_ptr, int ptr_wide, int64_t n_rows, const float* weight, int64_t n_edges, const void* sel, int sel_wide,
+                         const float* freq, int64_t n_sel, double* out2, int64_t* status, void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* The zeroth-order terms of a walk store (node_sequence [positions] int64, dag_num_nodes [walks] int64, dag_weight [walks] float32 as
+ * PathData.append_walks leaves them, src/pathpyG/core/path_data.py:126-159; n = 1 + the largest node id), in float64:
+ *   out2[0] = Z  = sum_w f_w log(c[first node of w] / positions), c the unweighted count of positions per node:
+ *     get_zeroth_order_log_likelihood, multi_order_model.py:311-336;
+ *   out2[1] = Z0 = sum_v C_v log(C_v / sum C), C_v the sum of the walk weights over the positions at v: the max_order = 0 branch of
+ *     get_mon_log_likelihood, :402-407.  The positions are grouped by node with one stable radix sort, so C_v is added in position order.
+ * Status bit 2 (an id of [0, n) without a position) or bit 0: the reference's torch.unique counts are then indexed by rank, not by id —
+ * the caller keeps the torch route.  ws: pp_mon_zeroth_llh_ws_bytes(positions, walks, n). */
+size_t pp_mon_zeroth_llh_ws_bytes(int64_t positions, int64_t walks, int64_t n);
+int pp_mon_zeroth_llh_f64(const int64_t* node_sequence, int64_t positions, const int64_t* dag_num_nodes, const float* dag_weight, int64_t walks,
+                          int64_t n, double* out2, int64_t* status, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1737,3 +1737,99 @@ def head_backward(dlogits: torch.Tensor, z: torch.Tensor, agg: torch.Tensor, x: 
                                            _p(d_agg), _p(dpre_fo), _p(colsum), _p(dw1), _p(dw2), _p(db1), _p(db2), _p(dwlin), _p(dblin), _p(ws), ws.numel(), _stream()),
               "pp_dbgnn_head_backward_f32")
     return d_agg, dpre_fo, colsum, dw1, dw2, db1, db2, dwlin, dblin
+
+
+# ------------------------------------------------------------------ order selection (csrc/pp_selection.hip)
+_INDEX_WIDE = {torch.int32: 0, torch.int64: 1}
+
+
+def _index_vector(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dtype not in _INDEX_WIDE:
+        raise TypeError(f"{what}: int32 or int64 expected, got {t.dtype}")
+    return t.reshape(-1).contiguous()
+
+
+def walk_counts(row_ptr: torch.Tensor, col: torch.Tensor, n: int, K: int) -> tuple[list, list]:
+    """``(totals, starts)`` as lists of Python ints for k = 1..K (pp_walk_counts_i64): ``totals[k - 1]`` the number of walks of length k of the
+    graph with source-major CSR ``row_ptr`` [n + 1] / ``col`` (int32 or int64 each), ``starts[k - 1]`` the number of nodes that start one — the
+    path counts of ``MultiOrderModel.get_mon_dof`` without a line-graph lift.  ``OverflowError`` when a count leaves int64 (the message names the
+    first such order; the error carries the saturated ``totals`` and the exact ``starts``); ``IndexError`` for a column outside [0, n), ``ValueError`` for a malformed ``row_ptr``."""
+    row_ptr, col = _index_vector(row_ptr, "walk_counts: row_ptr"), _index_vector(col, "walk_counts: col")
+    dev = require_device(row_ptr, col)
+    n, K = int(n), int(K)
+    if K < 1 or row_ptr.numel() != n + 1:
+        raise ValueError("walk_counts: K >= 1 and row_ptr of n + 1 entries expected")
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(3 * K + 1, dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_walk_counts_ws_bytes(n, col.numel(), K), dev)
+        check(L.pp_walk_counts_i64(_p(row_ptr), _INDEX_WIDE[row_ptr.dtype], _p(col), _INDEX_WIDE[col.dtype], n, col.numel(), K, _p(out), _p(ws),
+                                   ws.numel(), _stream()), "pp_walk_counts_i64")
+        out = out.tolist()
+    totals, starts, saturated, status = out[:K], out[K:2 * K], out[2 * K:3 * K], out[3 * K]
+    _bad_index(status, "walk_counts")
+    if status & 2:
+        raise ValueError("walk_counts: row_ptr is not an ascending pointer array over col")
+    if any(saturated):
+        k = saturated.index(1) + 1
+        error = OverflowError(f"walk_counts: the number of walks of length {k} does not fit int64")
+        error.totals, error.starts = totals, starts          # (saturated totals read INT64_MAX; the starts are exact)
+        raise error
+    return totals, starts
+
+
+def mon_layer_llh(row_ptr: torch.Tensor, weight: torch.Tensor, sel: torch.Tensor | None = None, freq: torch.Tensor | None = None) -> tuple[float, float]:
+    """``(T, I)`` of one layer in float64 (pp_mon_layer_llh_f64): ``T = sum_e w_e log(w_e / S_row(e))`` over the layer's source-major CSR
+    (``row_ptr`` int32 / int64, ``weight`` float32) and ``I = sum_s freq_s log(1 / outdegree(row of edge sel_s))`` for a selection of edge ids
+    (int32 / int64) with float32 ``freq`` (``None``: I = 0.0).  Bit-reproducible, and the same for either integer width."""
+    row_ptr = _index_vector(row_ptr, "mon_layer_llh: row_ptr")
+    weight = weight.contiguous()
+    if weight.dtype != torch.float32:
+        raise TypeError("mon_layer_llh: float32 weights expected")
+    n_sel = 0
+    if sel is not None:
+        sel, freq = _index_vector(sel, "mon_layer_llh: sel"), freq.contiguous()
+        if freq.dtype != torch.float32 or freq.numel() != sel.numel():
+            raise TypeError("mon_layer_llh: one float32 freq per selected edge expected")
+        n_sel = sel.numel()
+    dev = require_device(row_ptr, weight, sel, freq)
+    n_rows, n_edges = row_ptr.numel() - 1, weight.numel()
+    if n_rows < 0:
+        raise ValueError("mon_layer_llh: empty row_ptr")
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(3, dtype=torch.float64, device=dev)
+        ws = _workspace(L.pp_mon_layer_llh_ws_bytes(n_rows, n_edges, n_sel), dev)
+        check(L.pp_mon_layer_llh_f64(_p(row_ptr), _INDEX_WIDE[row_ptr.dtype], n_rows, _p(weight), n_edges, _p(sel),
+                                     0 if sel is None else _INDEX_WIDE[sel.dtype], _p(freq), n_sel, _p(out), out.data_ptr() + 16, _p(ws), ws.numel(),
+                                     _stream()), "pp_mon_layer_llh_f64")
+        host = out.cpu()
+    status = int(host[2:].view(torch.int64))
+    _bad_index(status, "mon_layer_llh: selected edge")
+    if status & 2:
+        raise ValueError("mon_layer_llh: row_ptr is not an ascending pointer array over the weights")
+    return float(host[0]), float(host[1])
+
+
+def mon_zeroth_llh(node_sequence: torch.Tensor, dag_num_nodes: torch.Tensor, dag_weight: torch.Tensor, n: int):
+    """``(Z, Z0)`` of a walk store in float64 (pp_mon_zeroth_llh_f64): the zeroth-order term of the walks' first nodes and the log-likelihood of
+    the zeroth-order model.  ``None`` when the reference's formula is not the one the kernel computes — a node id of [0, n) that never occurs or
+    one outside (``torch.unique``'s counts are then indexed by rank), walk lengths that do not fit the store: the caller takes the torch route."""
+    seq = node_sequence.reshape(-1).contiguous()
+    lengths, weight = dag_num_nodes.contiguous(), dag_weight.contiguous()
+    dev = require_device(seq, lengths, weight)
+    if seq.dtype != torch.int64 or lengths.dtype != torch.int64 or weight.dtype != torch.float32:
+        raise TypeError("mon_zeroth_llh: node_sequence / dag_num_nodes int64 and dag_weight float32 expected")
+    positions, walks, n = seq.numel(), lengths.numel(), int(n)
+    if positions == 0 or walks == 0 or n <= 0 or weight.numel() != walks or positions >= _INT32_ROWS or n >= _INT32_ROWS:
+        return None
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(3, dtype=torch.float64, device=dev)
+        ws = _workspace(L.pp_mon_zeroth_llh_ws_bytes(positions, walks, n), dev)
+        check(L.pp_mon_zeroth_llh_f64(_p(seq), positions, _p(lengths), _p(weight), walks, n, _p(out), out.data_ptr() + 16, _p(ws), ws.numel(),
+                                      _stream()), "pp_mon_zeroth_llh_f64")
+        host = out.cpu()
+    if int(host[2:].view(torch.int64)) != 0:
+        return None
+    return float(host[0]), float(host[1])

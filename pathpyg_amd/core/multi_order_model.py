@@ -5,7 +5,9 @@ Each layer ``k`` is a :class:`Graph` whose nodes are the distinct length-``k`` n
 input (walks or time-respecting paths) and whose weighted edges count their continuations.  All tensor work
 (event-graph lift, line-graph lifts, sequence extension, unique/coalesce) runs in HIP kernels; the
 higher-order ``IndexMap`` of every layer is created lazily instead of by a Python loop over nodes.
-The likelihood / order-selection methods (:243-509) reuse the lift kernels for their path counts.
+The likelihood / order-selection methods (:243-509) of a device-resident model run on kernels of their own
+(csrc/pp_selection.hip: walk counts without lifts, float64 likelihood terms straight from the layers' CSR); host-resident models and
+``NATIVE_SELECTION = False`` keep the chain of torch ops, which reuses the lift kernels for its path counts.
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ from .temporal_graph import TemporalGraph
 logger = logging.getLogger("pathpyg_amd")
 
 FUSED_BUILDER = True    # from_temporal_graph(max_order=2) on device-resident streams: the node-by-node order-2 builder (pp_debruijn2_*); False = generic kernels
+NATIVE_SELECTION = True    # get_mon_dof / the likelihood terms / estimate_order on device-resident models: pp_walk_counts_i64, pp_mon_*_llh_f64; False = torch ops
 
 
 class MultiOrderModel:
@@ -184,10 +187,15 @@ class MultiOrderModel:
     def get_mon_dof(self, max_order: Optional[int] = None, assumption: str = "paths") -> int:
         """Degrees of freedom of the multi-order model up to ``max_order`` (reference multi_order_model.py:243-309).
 
-        "paths": sum over k of the number of length-k paths of the first-order topology (k-1 line-graph lifts of layer 1)
-        minus, per order, the nodes that start at least one length-k path (their transition rows sum to one);
-        "ngrams": all ``n^k (n-1)`` combinations.  The reference counts the row constraint with a sparse matrix power; here
-        ``starts_k = A starts_{k-1} > 0`` is propagated instead — same count, no sparse-sparse product."""
+        "paths": sum over k of the number of length-k paths of the first-order topology minus, per order, the nodes that start at least
+        one length-k path (their transition rows sum to one); "ngrams": all ``n^k (n-1)`` combinations.
+        A device-resident layer 1 is counted by ``pp_walk_counts_i64``: one int64 vector pushed ``max_order`` times through its CSR gives
+        both numbers exactly, in Python ints — no line-graph lift, so orders whose 2^31 or more paths the lifts cannot hold are answered too;
+        ``OverflowError`` once a count leaves int64.  Otherwise (host tensors, ``NATIVE_SELECTION = False``) the paths are counted as the
+        reference does, by k-1 line-graph lifts of layer 1, and the row constraint by propagating ``starts_k = A starts_{k-1} > 0``."""
+        return self._mon_dof(max_order, assumption, None)
+
+    def _mon_dof(self, max_order: Optional[int], assumption: str, memo: Optional[dict]) -> int:
         if max_order is None:
             max_order = max(self.layers)
         if max_order > max(self.layers):
@@ -197,6 +205,9 @@ class MultiOrderModel:
         n = int(g1.data.num_nodes)
         dof = n - 1
         if assumption == "paths":
+            counts = self._walk_counts(max_order, memo)
+            if counts is not None:
+                return dof_from_walk_counts(n, counts[0], counts[1], max_order)
             edge_index = g1.data.edge_index
             for k in range(1, max_order + 1):
                 if k > 1:
@@ -218,8 +229,80 @@ class MultiOrderModel:
             raise ValueError(f"Unknown assumption {assumption}. Only 'path' and 'ngram' are accepted.")
         return int(dof)
 
+    def _walk_counts(self, max_order: int, memo: Optional[dict]):
+        """``(totals, starts)`` of layer 1's topology for the orders 1..``max_order`` (``_hip.walk_counts``), from ``memo`` when it holds enough
+        orders; ``None``: layer 1 is not on the device, or the switch is off."""
+        if not NATIVE_SELECTION:
+            return None
+        if max_order <= 0:
+            return [], []
+        if memo is not None and len(memo.get("counts", ((), ()))[0]) >= max_order:
+            return memo["counts"]
+        csr = _selection_csr(self.layers[1], need_weight=False)
+        if csr is None:
+            return None
+        row_ptr, col, _ = csr
+        counts = _hip.walk_counts(row_ptr, col, int(self.layers[1].data.num_nodes), max_order)
+        if memo is not None:
+            memo["counts"] = counts
+        return counts
+
+    def _zeroth_terms(self, dag_graph: Data, memo: Optional[dict]):
+        """``(Z, Z0)`` of the walk store from ``pp_mon_zeroth_llh_f64`` or ``None`` (walks not on the device with their stock dtypes, node ids
+        with gaps, the switch off): then the torch ops run."""
+        if memo is not None and "zeroth" in memo:
+            return memo["zeroth"]
+        out = None
+        if _native_walks(dag_graph):
+            out = _hip.mon_zeroth_llh(dag_graph.node_sequence, dag_graph.dag_num_nodes, dag_graph.dag_weight, int(self.layers[1].data.num_nodes))
+        if memo is not None:
+            memo["zeroth"] = out
+        return out
+
+    def _layer_terms(self, dag_graph: Data, order: int, want_intermediate: bool, memo: Optional[dict]):
+        """``(T, I)`` of layer ``order`` from ONE ``pp_mon_layer_llh_f64`` call — the top-order term and, with ``want_intermediate``, the
+        contribution of every walk's first order-``order`` transition — or ``None`` when the layer or the walks are not on the device with
+        their stock dtypes (or the switch is off).  ``I`` is ``None`` when it was not asked for, and when the NEXT layer's ``inverse_idx`` is
+        not on the device: the layer's own term stays native, only the intermediate term takes the torch route."""
+        key = ("layer", order)
+        if memo is not None and key in memo and (memo[key] is None or memo[key][1] is not None or not want_intermediate
+                                                 or ("no inverse", order) in memo):
+            return memo[key]
+        out = None
+        if _native_walks(dag_graph):
+            csr = _selection_csr(self.layers[order], need_weight=True)
+            sel = freq = None
+            if csr is not None and want_intermediate:
+                inverse = _selection_inverse(self.layers[order + 1])
+                if inverse is None:
+                    want_intermediate = False
+                    if memo is not None:
+                        memo["no inverse", order] = True
+                else:
+                    # first instance of every walk that still has one at this order (reference :352-361): a walk of L nodes holds L - order of them
+                    lengths_ho = dag_graph.dag_num_nodes - order
+                    keep = lengths_ho > 0
+                    kept = lengths_ho[keep]
+                    sel = inverse[torch.cumsum(kept, 0) - kept]
+                    freq = dag_graph.dag_weight[keep]
+            if csr is not None:
+                t, i = _hip.mon_layer_llh(csr[0], csr[2], sel, freq)
+                out = (t, i if want_intermediate else None)
+        if memo is not None:
+            memo[key] = out
+        return out
+
     def get_zeroth_order_log_likelihood(self, dag_graph: Data) -> float:
-        """Log-likelihood of the walks' first nodes under the node-frequency model (reference multi_order_model.py:311-336)."""
+        """Log-likelihood of the walks' first nodes under the node-frequency model (reference multi_order_model.py:311-336).
+        On a device-resident walk store whose node ids are exactly 0..n-1: the float64 sum of the same formula (``pp_mon_zeroth_llh_f64``),
+        where the torch ops sum in float32.  The kernel takes the walks' first positions from ``dag_num_nodes``, the torch ops from
+        ``edge_index``: the store is assumed to be as ``PathData.append_walks`` leaves it, where the two agree."""
+        return self._zeroth_order_llh(dag_graph, None)
+
+    def _zeroth_order_llh(self, dag_graph: Data, memo: Optional[dict]) -> float:
+        native = self._zeroth_terms(dag_graph, memo)
+        if native is not None:
+            return native[0]
         frequencies = dag_graph.dag_weight
         is_start = torch.ones(dag_graph.num_nodes, dtype=torch.bool, device=frequencies.device)
         is_start[dag_graph.edge_index[1]] = False
@@ -229,7 +312,15 @@ class MultiOrderModel:
         return torch.mul(frequencies, torch.log(emission[start_nodes])).sum().item()
 
     def get_intermediate_order_log_likelihood(self, dag_graph: Data, order: int) -> float:
-        """Contribution of the first order-``order`` transition of every walk (reference multi_order_model.py:338-369)."""
+        """Contribution of the first order-``order`` transition of every walk (reference multi_order_model.py:338-369).
+        On a device-resident model: the float64 sum of the same formula (``pp_mon_layer_llh_f64``, the row of a transition found in the
+        layer's CSR), where the torch ops sum in float32."""
+        return self._intermediate_order_llh(dag_graph, order, None)
+
+    def _intermediate_order_llh(self, dag_graph: Data, order: int, memo: Optional[dict]) -> float:
+        native = self._layer_terms(dag_graph, order, True, memo)
+        if native is not None and native[1] is not None:
+            return native[1]
         frequencies = dag_graph.dag_weight
         lengths_ho = dag_graph.dag_num_nodes - order                 # walks shrink by `order` nodes in order-k encoding
         keep = lengths_ho > 0
@@ -241,14 +332,24 @@ class MultiOrderModel:
 
     def get_mon_log_likelihood(self, dag_graph: Data, max_order: int = 1) -> float:
         """Log-likelihood of the walks under the multi-order model with layers 0..``max_order``
-        (reference multi_order_model.py:371-409)."""
+        (reference multi_order_model.py:371-409): the zeroth-order term, the intermediate terms of the orders below ``max_order`` and the
+        top layer's term, added left to right.  On a device-resident model every term is the float64 sum of its formula (see the term
+        methods), where the torch ops sum in float32."""
+        return self._mon_llh(dag_graph, max_order, None)
+
+    def _mon_llh(self, dag_graph: Data, max_order: int, memo: Optional[dict]) -> float:
         if max_order > 0:
-            llh = self.get_zeroth_order_log_likelihood(dag_graph)
-            for order in range(1, max_order):
-                llh += self.get_intermediate_order_log_likelihood(dag_graph, order)
+            zeroth = self._zeroth_order_llh(dag_graph, memo)
+            intermediate = [self._intermediate_order_llh(dag_graph, order, memo) for order in range(1, max_order)]
+            native = self._layer_terms(dag_graph, max_order, False, memo)
+            if native is not None:
+                return llh_from_terms(zeroth, intermediate, native[0])
             top = self.layers[max_order]
             probs = top.transition_probabilities(edge_attr="edge_weight")
-            return llh + (torch.log(probs) * top.data.edge_weight).sum().item()
+            return llh_from_terms(zeroth, intermediate, (torch.log(probs) * top.data.edge_weight).sum().item())
+        native = self._zeroth_terms(dag_graph, memo)
+        if native is not None:
+            return native[1]
         frequencies = dag_graph.dag_weight
         counts = torch.bincount(dag_graph.node_sequence.squeeze(), frequencies.repeat_interleave(dag_graph.dag_num_nodes))
         emission = counts / counts.sum()
@@ -257,7 +358,11 @@ class MultiOrderModel:
     def likelihood_ratio_test(self, dag_graph: Data, max_order_null: int = 0, max_order: int = 1, assumption: str = "paths",
                               significance_threshold: float = 0.01) -> tuple:
         """Likelihood-ratio test of order ``max_order`` against ``max_order_null`` (reference multi_order_model.py:411-459):
-        ``(null rejected?, p-value)`` with ``x = -2 (log L0 - log L1)`` chi-square distributed in the dof difference."""
+        ``(null rejected?, p-value)`` with ``x = -2 (log L0 - log L1)`` chi-square distributed in the dof difference.
+        The terms the two likelihoods share and the walk counts of the two dof are computed once."""
+        return self._ratio_test(dag_graph, max_order_null, max_order, assumption, significance_threshold, {})
+
+    def _ratio_test(self, dag_graph: Data, max_order_null: int, max_order: int, assumption: str, significance_threshold: float, memo: dict) -> tuple:
         if max_order_null >= max_order:
             logger.error("order of null hypothesis must be smaller than order of alternative hypothesis")
             raise ValueError("order of null hypothesis must be smaller than order of alternative hypothesis")
@@ -265,14 +370,15 @@ class MultiOrderModel:
             logger.error("order of hypotheses must be smaller than max. order of MultiOrderModel")
             raise ValueError(f"order of hypotheses ({max_order_null} and {max_order}) must be smaller than max. order of "
                              f"MultiOrderModel {max(self.layers)}")
-        x = -2 * (self.get_mon_log_likelihood(dag_graph, max_order=max_order_null)
-                  - self.get_mon_log_likelihood(dag_graph, max_order=max_order))
-        dof_diff = self.get_mon_dof(max_order, assumption=assumption) - self.get_mon_dof(max_order_null, assumption=assumption)
+        x = -2 * (self._mon_llh(dag_graph, max_order_null, memo) - self._mon_llh(dag_graph, max_order, memo))
+        dof_diff = self._mon_dof(max_order, assumption, memo) - self._mon_dof(max_order_null, assumption, memo)
         p = 1 - chi2.cdf(x, dof_diff)
         return (p < significance_threshold), p
 
     def estimate_order(self, dag_data: PathData, max_order: Optional[int] = None, significance_threshold: float = 0.01) -> int:
-        """Highest order whose layer significantly improves the likelihood of the walks (reference multi_order_model.py:461-509)."""
+        """Highest order whose layer significantly improves the likelihood of the walks (reference multi_order_model.py:461-509):
+        the last k in 2..``max_order`` whose :meth:`likelihood_ratio_test` against k-1 rejects.  One pass: every likelihood term and the
+        walk counts are computed once for all the tests (each layer's top and intermediate term come out of one kernel call)."""
         if max_order is None:
             max_order = max(self.layers)
         if max_order > max(self.layers):
@@ -285,10 +391,14 @@ class MultiOrderModel:
         if not set(dag_data.mapping.node_ids).issubset(ours):
             logger.error("Input paths do not have same set of nodes as multi-order network")
             raise ValueError("Input paths do not have same set of nodes as multi-order network")
+        memo: dict = {}
+        self._walk_counts(max_order, memo)                            # all orders in one call; the tests below read prefixes of it
+        for k in range(1, max_order):
+            if k in self.layers and k + 1 in self.layers:
+                self._layer_terms(dag_data.data, k, True, memo)       # T_k and I_k together; T of the top order comes with its test
         accepted = 1
         for k in range(2, max_order + 1):
-            if self.likelihood_ratio_test(dag_data.data, max_order_null=k - 1, max_order=k,
-                                          significance_threshold=significance_threshold)[0]:
+            if self._ratio_test(dag_data.data, k - 1, k, "paths", significance_threshold, memo)[0]:
                 accepted = k
         return accepted
 
@@ -392,6 +502,95 @@ class MultiOrderModel:
         return built
 
 
+def dof_from_walk_counts(n: int, totals: list, starts: list, max_order: int) -> int:
+    """Degrees of freedom of the "paths" assumption (reference multi_order_model.py:283-309) from the walk counts of the first-order topology:
+    ``n - 1`` for order 0 plus, per order k <= ``max_order``, the walks of length k (``totals[k - 1]``) minus the nodes that start one
+    (``starts[k - 1]``: a row of the order-k transition matrix sums to one).  Python ints: exact at any size."""
+    return int(n) - 1 + sum(int(t) for t in totals[:max_order]) - sum(int(s) for s in starts[:max_order])
+
+
+def llh_from_terms(zeroth: float, intermediate: list, top: float) -> float:
+    """Log-likelihood of the model with layers 0..k from its terms (reference multi_order_model.py:385-397): the zeroth-order term of the
+    walks' first nodes, the intermediate terms of the orders 1..k-1 and the top layer's term, added left to right."""
+    llh = zeroth
+    for term in intermediate:
+        llh += term
+    return llh + top
+
+
+def _still(current, made: Lazy) -> bool:
+    """Whether a bag still holds what a builder put there: the deferred tensor itself, or its value, not edited in place since."""
+    return current is made or (made.value is not None and current is made.value and current._version == made.version)
+
+
+# A layer of a fast builder carries `_pp_csr` = (the builder's MultiOrderLayer, the deferred edge_index and the version of the edge_weight it was
+# made with, the deferred inverse_idx, the builder's int32 inverse_idx): a second view of the layer beside Graph._csr, valid only while the bag
+# still holds exactly those objects.  It stops being used — the kernels then read Graph.row_ptr / col / edge_weight / inverse_idx — when
+# data.edge_index, data.edge_weight or data.inverse_idx is REPLACED (assignment, Graph.to / Data.to, clone), when the read edge_index, edge_weight
+# or inverse_idx tensor is EDITED IN PLACE (its _version moves), or when data.num_nodes changes.  Nothing else is looked at.
+def _note_csr(graph: Graph, b, weight, inverse32=None) -> None:
+    """Remember the builder's CSR arrays of a layer for the order-selection kernels (:func:`_selection_csr`), with what tells whether the
+    layer's tensors are still the ones they describe.  ``inverse32``: the builder's int32 ``inverse_idx`` behind the bag's deferred int64 view."""
+    if isinstance(weight, torch.Tensor) and weight is b.weight:
+        d = graph.data
+        graph._pp_csr = (b, d.peek("edge_index"), weight._version, d.peek("inverse_idx"), inverse32)
+
+
+def _builder_csr(graph: Graph):
+    """The :class:`~pathpyg_amd._hip.MultiOrderLayer` a fast builder left behind ``graph`` while ``edge_index`` and ``edge_weight`` still are
+    what it made (deferred or read, neither replaced nor edited in place); else ``None``."""
+    rec = getattr(graph, "_pp_csr", None)
+    if rec is None:
+        return None
+    b, index, weight_version = rec[:3]
+    d = graph.data
+    weight = d.peek("edge_weight")
+    if not isinstance(index, Lazy) or not _still(d.peek("edge_index"), index) or weight is not b.weight or weight._version != weight_version:
+        return None
+    return b if int(d.num_nodes) == b.n_nodes else None
+
+
+def _selection_csr(graph: Graph, need_weight: bool):
+    """``(row_ptr, col, weight)`` of a device-resident layer for the order-selection kernels: the builder's int32 arrays when the layer came
+    out of a fast builder (its deferred ``edge_index`` stays deferred), else ``Graph.row_ptr`` / ``col`` (int64) and ``edge_weight``.
+    ``None``: tensors on the host, or (``need_weight``) weights that are not float32."""
+    b = _builder_csr(graph)
+    if b is not None and b.row_ptr.is_cuda:
+        return b.row_ptr[:b.n_nodes + 1], b.col, b.weight
+    ei = _dispatch.plain(graph.data.edge_index)
+    if not isinstance(ei, torch.Tensor) or not ei.is_cuda or ei.dtype != torch.int64:
+        return None
+    weight = graph.data.edge_weight
+    if need_weight and not (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dtype == torch.float32 and weight.dim() == 1
+                            and weight.numel() == ei.size(1)):
+        return None
+    return graph.row_ptr, graph.col, weight
+
+
+def _selection_inverse(graph: Graph):
+    """``inverse_idx`` of a device-resident layer as an int32 / int64 vector — the builder's own int32 one while the bag's deferred view of it
+    is untouched — or ``None``."""
+    rec = getattr(graph, "_pp_csr", None)
+    current = graph.data.peek("inverse_idx")
+    if rec is not None and rec[4] is not None and isinstance(rec[3], Lazy) and _still(current, rec[3]):
+        return rec[4]
+    inverse = graph.data.inverse_idx
+    if isinstance(inverse, torch.Tensor) and inverse.is_cuda and inverse.dtype in (torch.int32, torch.int64) and inverse.dim() == 1:
+        return inverse
+    return None
+
+
+def _native_walks(dag_graph: Data) -> bool:
+    """Whether the order-selection kernels take this walk store: the switch is on and the walks' tensors are on the device with their stock dtypes."""
+    if not NATIVE_SELECTION:
+        return False
+    for name, dtype in (("node_sequence", torch.int64), ("dag_num_nodes", torch.int64), ("dag_weight", torch.float32)):
+        t = dag_graph.peek(name) if isinstance(dag_graph, Data) else getattr(dag_graph, name, None)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype:
+            return False
+    return True
+
+
 def _csr_rows(ptr: torch.Tensor, total: int) -> torch.Tensor:
     """Row id of every entry of a CSR with int32 row pointers ``ptr`` (int64 [total])."""
     n = ptr.numel() - 1
@@ -461,6 +660,7 @@ def _csr_layers(g: TemporalGraph, ei: torch.Tensor, csr: list, cached: bool, wei
         if cached or k == len(csr):
             d = Data(edge_index=index, num_nodes=b.n_nodes, node_sequence=seq, edge_weight=weight, inverse_idx=inverse)
             layers[k] = Graph._from_parts(d, g.mapping if k == 1 else IndexMap.from_node_sequence(g.mapping, seq))
+            _note_csr(layers[k], b, weight)
             if k == 2:
                 layers[k]._nodes_are_fo_edges = True
     return layers
@@ -499,6 +699,7 @@ def _path_csr_layers(mapping: IndexMap, node_sequence: torch.Tensor, csr: list, 
         if cached or k == 1 or k == len(csr):
             d = Data(edge_index=index, num_nodes=b.n_nodes, node_sequence=seq, edge_weight=b.weight, inverse_idx=inverse)
             layers[k] = Graph._from_parts(d, mapping if k == 1 else IndexMap.from_node_sequence(mapping, seq))
+            _note_csr(layers[k], b, b.weight, inv32 if k >= 2 else None)
     return layers
 
 
