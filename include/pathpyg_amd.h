@@ -518,6 +518,30 @@ size_t pp_cross_entropy_ws_bytes(void);       /* per-workgroup partial sums, add
 int pp_cross_entropy_f32(const float* logits, const int64_t* target, int64_t n, int C, float* loss, float* dlogits, void* ws, size_t ws_bytes,
                          pp_stream_t stream);
 
+/* The same loss over a SELECTION of the rows, with class weights - the objective of a semi-supervised node classifier (the reference's
+ * tutorial loop trains on out[train_mask], docs/tutorial/netzschleuder.ipynb cells 15-17) without the boolean-index gather, its nonzero
+ * read-back and the index_put backward.  Row i is selected iff (mask == NULL or mask[i] != 0) and (use_ignore == 0 or
+ * target[i] != ignore_index); mask holds one byte per row, weight [C] fp32 may be NULL (all ones).
+ *   dlogits_raw [n,C] (may be NULL) = w[y_i] (softmax(z_i) - onehot(y_i)) on selected rows, exactly 0.0f on every other row: the
+ *                gradient of the SUM reduction; the mean's is dlogits_raw * inv_den.
+ *   result     : 32 bytes on the device, 8-byte aligned: float num = sum w[y_i] nll_i, float den = sum w[y_i], float mean = num / den (NaN on
+ *                an empty selection), float inv_den = 1 / den (0 when no valid row is selected), int64 selected rows, int64 selected
+ *                rows whose target lies outside [0, C).
+ * A selected row with an out-of-range target contributes nothing and gets a zero gradient row; no target is used as an index before that
+ * test, unselected rows may hold any target and their logits are not loaded.  Per-row arithmetic as pp_cross_entropy_f32.  No float atomics:
+ * per-workgroup partials (ws) are added in a fixed order, the same inputs give the same bits on every call; dlogits_raw does not depend on
+ * the grid at all.  The grid follows pp_set_launch_share. */
+size_t pp_cross_entropy_masked_ws_bytes(void);
+int pp_cross_entropy_masked_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
+                                int64_t ignore_index, int use_ignore, void* result, float* dlogits_raw, void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* Confusion matrix of the predictions under the same selection: counts [C,C] int64 (zeroed by the callee), row = true class, column =
+ * predicted class = the lowest column holding the row maximum, a NaN counting as the maximum (numpy's argmax).  status [1] int64 (zeroed by
+ * the callee) = selected rows skipped because their target lies outside [0, C).  Per-workgroup histograms in LDS, flushed with integer
+ * atomics: the result does not depend on the order.  1 <= C <= 64. */
+int pp_confusion_f32(const float* logits, const int64_t* target, const uint8_t* mask, int64_t n, int C, int64_t ignore_index, int use_ignore,
+                     int64_t* counts, int64_t* status, pp_stream_t stream);
+
 /* One Adam step (step = 1, 2, ...) over ALL n_tensors fp32 parameter tensors in one launch per 24 tensors: HOST arrays of DEVICE pointers
  * (params, grads, exp_avg, exp_avg_sq) and of element counts.  The update of torch.optim.Adam (amsgrad off, maximize off; weight_decay is
  * the L2 form g + wd*p).  No reference counterpart: pathpyG ships the model (nn/dbgnn.py:72-151); its only training loop is the upstream tutorial

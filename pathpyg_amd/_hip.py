@@ -10,6 +10,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -1665,6 +1666,69 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, want_grad: bool = 
         ws = _workspace(L.pp_cross_entropy_ws_bytes(), dev)
         check(L.pp_cross_entropy_f32(_p(logits), _p(target), n, c, _p(loss), _p(grad), _p(ws), ws.numel(), _stream()), "pp_cross_entropy_f32")
     return loss[0], grad
+
+
+class MaskedSums(NamedTuple):
+    """The 32-byte device result of pp_cross_entropy_masked_f32, as two views of one buffer."""
+    values: torch.Tensor      # float32 [4]: sum w[y] nll, sum w[y], their quotient (the mean loss), 1 / sum w[y] (0: nothing valid selected)
+    counts: torch.Tensor      # int64 [2]: selected rows, selected rows whose target lies outside [0, C)
+
+
+def _selection(what: str, n: int, c: int, target, mask, weight=None):
+    target = target.contiguous()
+    if target.dtype != torch.int64 or target.dim() != 1 or target.numel() != n:
+        raise ValueError(f"{what}: target must be int64 [{n}]")
+    if mask is not None:
+        if mask.dtype != torch.bool or mask.dim() != 1 or mask.numel() != n:
+            raise ValueError(f"{what}: mask must be bool [{n}]")
+        mask = mask.contiguous()
+    if weight is not None:
+        if weight.dtype != torch.float32 or weight.dim() != 1 or weight.numel() != c:
+            raise ValueError(f"{what}: weight must be float32 [{c}]")
+        weight = weight.contiguous()
+    return target, mask, weight
+
+
+def cross_entropy_masked(logits: torch.Tensor, target: torch.Tensor, mask: torch.Tensor | None = None, weight: torch.Tensor | None = None,
+                         ignore_index: int | None = None, want_grad: bool = True):
+    """``(sums, raw_grad)`` of the class-weighted cross-entropy over the rows that ``mask`` (bool [N]; None: all) and ``ignore_index``
+    (None: unused) select, in one pass and without a read-back: ``sums`` is a :class:`MaskedSums` on the device, ``raw_grad`` [N, C]
+    (None without ``want_grad``) the gradient of the SUM reduction — ``w[y] (softmax - onehot)`` on selected rows, exact zeros elsewhere;
+    the mean's gradient is ``raw_grad * sums.values[3]``.  logits [N, C<=64] fp32, target int64 [N], weight fp32 [C] or None."""
+    dev = require_device(logits, target, mask, weight)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("cross_entropy_masked: logits must be float32 [N, C]")
+    logits = logits.contiguous()
+    n, c = logits.shape
+    target, mask, weight = _selection("cross_entropy_masked", n, c, target, mask, weight)
+    with torch.cuda.device(dev):
+        result = torch.empty(4, dtype=torch.int64, device=dev)
+        grad = torch.empty_like(logits) if want_grad else None
+        L = lib()
+        ws = _workspace(L.pp_cross_entropy_masked_ws_bytes(), dev)
+        check(L.pp_cross_entropy_masked_f32(_p(logits), _p(target), _p(mask), _p(weight), n, c, 0 if ignore_index is None else int(ignore_index),
+                                            0 if ignore_index is None else 1, _p(result), _p(grad), _p(ws), ws.numel(), _stream()),
+              "pp_cross_entropy_masked_f32")
+    return MaskedSums(result[:2].view(torch.float32), result[2:]), grad
+
+
+def confusion(logits: torch.Tensor, target: torch.Tensor, mask: torch.Tensor | None = None, ignore_index: int | None = None,
+              with_status: bool = False):
+    """Confusion matrix int64 [C, C] (row = true class, column = predicted class) of ``argmax(logits, 1)`` over the selected rows — the
+    selection of :func:`cross_entropy_masked`; the prediction is the lowest column holding the row maximum, a NaN counting as the maximum.
+    ``with_status``: the flat int64 [C*C + 1] buffer instead, whose last word counts the selected rows skipped for a target outside
+    [0, C) (one read-back gives both)."""
+    dev = require_device(logits, target, mask)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("confusion: logits must be float32 [N, C]")
+    logits = logits.contiguous()
+    n, c = logits.shape
+    target, mask, _ = _selection("confusion", n, c, target, mask)
+    with torch.cuda.device(dev):
+        buf = torch.empty(c * c + 1, dtype=torch.int64, device=dev)
+        check(lib().pp_confusion_f32(_p(logits), _p(target), _p(mask), n, c, 0 if ignore_index is None else int(ignore_index),
+                                     0 if ignore_index is None else 1, _p(buf), _p(buf[c * c:]), _stream()), "pp_confusion_f32")
+    return buf if with_status else buf[: c * c].view(c, c)
 
 
 def dense_backward(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, fuse_act: bool, want_input_grad: bool, want_colsum: bool,

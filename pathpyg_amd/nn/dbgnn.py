@@ -20,7 +20,9 @@ segment reduction over the rows of ``W^T``.  All tensors must live on the GPU; f
 from __future__ import annotations
 
 import math
+import weakref
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 from torch.nn import Linear, Module, ModuleList, Parameter
@@ -387,7 +389,7 @@ class _CrossEntropy(torch.autograd.Function):
         return grad * dloss, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+def _cross_entropy_all_rows(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Mean softmax cross-entropy (``F.cross_entropy`` semantics for class-index targets) with its gradient computed in the
     same HIP pass; falls back to torch for CPU tensors or more than 64 classes."""
     if (logits.is_cuda and logits.dim() == 2 and logits.dtype == torch.float32 and logits.size(1) <= 64 and logits.size(0) > 0
@@ -413,6 +415,132 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if lo >= 0 and hi < logits.size(1):
             return _CrossEntropy.apply(logits, target)
     return F.cross_entropy(logits, target)
+
+
+class _MaskedCrossEntropy(torch.autograd.Function):
+    """Loss over the selected rows (pp_cross_entropy_masked_f32).  Saved for backward: the gradient of the SUM reduction and, for the
+    mean, the device scalar 1 / denominator — no host read-back on either side.  Second output: the kernel's two counters."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mask, weight, ignore_index, mean: bool):
+        sums, raw = _hip.cross_entropy_masked(logits, target, mask, weight, ignore_index, want_grad=ctx.needs_input_grad[0])
+        ctx.mean = mean
+        ctx.save_for_backward(raw, sums.values[3])
+        ctx.mark_non_differentiable(sums.counts)
+        return sums.values[2 if mean else 0], sums.counts
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        raw, inv_den = ctx.saved_tensors
+        return raw * (dloss * inv_den if ctx.mean else dloss), None, None, None, None, None
+
+
+def _base_of(t: torch.Tensor) -> torch.Tensor:
+    return t._base if t._base is not None else t
+
+
+def _view_key(t: torch.Tensor) -> tuple:
+    return (t.storage_offset(), t.numel(), tuple(t.stride()), t._version)
+
+
+def _check_selected_targets(counts: torch.Tensor, target: torch.Tensor, mask, ignore_index, num_classes: int) -> None:
+    """Raises IndexError when a selected row's target lies outside [0, C).  The kernel's counter is read once per (target storage / slice /
+    version, mask storage / slice / version, ignore_index, C) — the record lives on the target's base tensor, as ``_pp_class_range``
+    does, and holds the mask's base weakly so that another tensor at a recycled address is not mistaken for it."""
+    holder = _base_of(target)
+    mask_base = None if mask is None else _base_of(mask)
+    key = (_view_key(target), None if mask is None else (id(mask_base),) + _view_key(mask), ignore_index, num_classes)
+    seen = getattr(holder, "_pp_selected_range", None)
+    if not isinstance(seen, dict):
+        seen = {}
+        try:
+            holder._pp_selected_range = seen
+        except Exception:
+            pass
+    hit = seen.get(key)
+    if hit is None or (mask_base is not None and hit[0]() is not mask_base):
+        if len(seen) > 64:
+            seen.clear()
+        hit = seen[key] = (None if mask_base is None else weakref.ref(mask_base), int(counts[1]))
+    if hit[1]:
+        raise IndexError(f"cross_entropy: {hit[1]} selected target(s) outside [0, {num_classes})")
+
+
+def _native_selection(logits, target, mask, ignore_index) -> bool:
+    return (logits.is_cuda and logits.dim() == 2 and logits.dtype == torch.float32 and 1 <= logits.size(1) <= 64
+            and isinstance(target, torch.Tensor) and target.is_cuda and target.dim() == 1 and target.dtype == torch.int64
+            and target.size(0) == logits.size(0)
+            and (mask is None or (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype == torch.bool and mask.dim() == 1
+                                  and mask.size(0) == logits.size(0)))
+            and (ignore_index is None or isinstance(ignore_index, int)))
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, *, mask=None, weight=None, ignore_index=None, reduction: str = "mean") -> torch.Tensor:
+    """Softmax cross-entropy of class-index targets, forward and gradient in one HIP pass.
+
+    With no keyword it is the mean over all rows (``F.cross_entropy(logits, target)``).  With ``mask`` (bool [N]), ``weight`` (fp32 [C]),
+    ``ignore_index`` or ``reduction`` ("mean" / "sum") it is the loss of a semi-supervised node classifier,
+
+        F.cross_entropy(logits[mask], target[mask], weight=weight, ignore_index=ignore_index, reduction=reduction)
+
+    computed WITHOUT the gather: the selection is a predicate inside the kernel, the gradient comes back as a full [N, C] with exact
+    zeros on unselected rows, and no step reads anything back to the host — ``loss = cross_entropy(model(data), data.y,
+    mask=data.train_mask)``.  Unselected rows may hold any target (-1, -100, ...).  A selected target outside [0, C) raises IndexError
+    (looked for once per target / mask / ignore_index, not per step).  An empty selection gives a NaN mean and a zero gradient, as torch.
+    ``ignore_index=None``: no value is ignored (the torch form, which cannot switch the test off, then runs with torch's default, -100).
+    CPU tensors, more than 64 classes, a non-bool mask, a non-fp32 weight and soft labels run the torch expression above."""
+    if mask is None and weight is None and ignore_index is None and reduction == "mean":
+        return _cross_entropy_all_rows(logits, target)
+    if reduction not in ("mean", "sum"):
+        raise ValueError(f"cross_entropy: reduction must be 'mean' or 'sum', got {reduction!r}")
+    if (_native_selection(logits, target, mask, ignore_index)
+            and (weight is None or (isinstance(weight, torch.Tensor) and weight.is_cuda and weight.dtype == torch.float32
+                                    and tuple(weight.shape) == (logits.size(1),) and not weight.requires_grad))):
+        loss, counts = _MaskedCrossEntropy.apply(logits, target, mask, weight, ignore_index, reduction == "mean")
+        _check_selected_targets(counts, target, mask, ignore_index, logits.size(1))
+        return loss
+    if mask is not None:
+        logits, target = logits[mask], target[mask]
+    return F.cross_entropy(logits, target, weight=weight, ignore_index=-100 if ignore_index is None else ignore_index, reduction=reduction)
+
+
+def evaluate(logits: torch.Tensor, target: torch.Tensor, *, mask=None, ignore_index=None) -> dict:
+    """Scores of ``argmax(logits, 1)`` against ``target`` over the rows that ``mask`` / ``ignore_index`` select (the selection of
+    :func:`cross_entropy`): ``confusion`` (int64 [C, C] on the logits' device, row = true class, column = predicted class), ``support``
+    (int64 [C], rows per true class), ``accuracy``, ``balanced_accuracy`` (mean recall over the classes with support) and ``macro_f1``
+    (mean F1 over the classes with support or predictions).  On the GPU the matrix is one HIP pass (pp_confusion_f32) and the scores come
+    from ONE read-back of it; ties go to the lowest class and a NaN counts as the row maximum (numpy's ``argmax``).  A selected target
+    outside [0, C) raises IndexError."""
+    c = logits.size(1)
+    if _native_selection(logits, target, mask, ignore_index):
+        buf = _hip.confusion(logits.detach(), target, mask, ignore_index, with_status=True)
+        host = buf.cpu().numpy()
+        conf, bad = host[: c * c].reshape(c, c), int(host[c * c])
+        confusion = buf[: c * c].view(c, c)
+    else:
+        z, y = logits.detach().float().cpu().numpy(), target.cpu().numpy()
+        keep = np.ones(y.shape[0], dtype=bool) if mask is None else mask.cpu().numpy().astype(bool)
+        if ignore_index is not None:
+            keep &= y != ignore_index
+        z, y = z[keep], y[keep]
+        bad = int(((y < 0) | (y >= c)).sum())
+        conf = np.zeros((c, c), dtype=np.int64)
+        if not bad and y.size:
+            np.add.at(conf, (y, np.argmax(z, axis=1)), 1)
+        confusion = torch.from_numpy(conf).to(logits.device)
+    if bad:
+        raise IndexError(f"evaluate: {bad} selected target(s) outside [0, {c})")
+    conf = conf.astype(np.float64)
+    support, predicted, hit = conf.sum(1), conf.sum(0), np.diag(conf)
+    total = support.sum()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recall = hit[support > 0] / support[support > 0]
+        seen = (support + predicted) > 0
+        f1 = 2.0 * hit[seen] / (support[seen] + predicted[seen])
+        return {"confusion": confusion, "support": torch.from_numpy(support.astype(np.int64)),
+                "accuracy": float(hit.sum() / total) if total else float("nan"),
+                "balanced_accuracy": float(recall.mean()) if recall.size else float("nan"),
+                "macro_f1": float(f1.mean()) if f1.size else float("nan")}
 
 
 def _plan_cache(data) -> dict:
