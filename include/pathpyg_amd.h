@@ -255,6 +255,34 @@ int pp_multiorder_prepare_range(const int64_t* edge_index, int64_t m, int64_t nu
                                 int32_t* ibase, int32_t* tlast, float* w, int32_t* rowptr, void* ws, size_t ws_bytes, pp_stream_t stream);
 int pp_multiorder_stitch(const int32_t* gathered, int64_t stride, int64_t last_at, int world, const int64_t* row_lo, const int64_t* edge_lo,
                          int32_t* cand_ptr, int32_t* cand_last, pp_stream_t stream);
+/* A level in PASSES on one GPU: a level with more children than int32 ids hold (or than a budget of the caller's) is cut into contiguous ranges
+ * of whole types, pp_multiorder_step runs unchanged on one range after another (tptr / ibase of the range numbered from 0, col / cand_ptr /
+ * cand_last / tab global), and the ranges' layer pieces are joined.  The reference has no such limit: its lifts are int64 throughout
+ * (src/pathpyG/algorithms/lift_order.py:65,76).
+ *
+ * pp_multiorder_split: the cuts of a level of n_types types and the rebased arrays of all parts, one launch sequence, no read-back.  ibase
+ *   [n_types + 1] may be WRAPPED (a level with 2^31 or more children: the scan stores the low 32 bits of int64 sums); every single count is
+ *   below 2^31 (the step clamps and sets status bit 2 otherwise), so the counts are the unsigned differences of neighbouring entries and their
+ *   prefix is taken in int64.  Greedy rule: a part that starts at type t0 ends before the first type t with prefix[t + 1] - prefix[t0] >
+ *   budget, holds at least one type; a single type above the budget is a part of its own.  report: int64 [4 + 3 * (max_parts + 1)] =
+ *   {parts, status, children of the level, children of the largest part}, then three rows of max_parts + 1 entries of which parts + 1 are
+ *   written: first type of part p, children before it, instances before it (tptr there).  tptr_out / ibase_out: int32 [n_types + max_parts];
+ *   part p's types_p + 1 entries start at entry (first type of p) + p.  max_parts <= min(n_types, 65536): one lane walks the cuts, a
+ *   bisection per part; the split is meant for two to a few hundred parts.  status bit 0: more than max_parts parts (2 * children /
+ *   budget + 2 always suffice: two neighbouring parts together exceed the budget); bit 1: a single type with 2^31 - 16 or more children; bit 2: ibase is
+ *   not the low 32 bits of an ascending prefix of counts below 2^31.  With a bit set the rebased arrays are not written.
+ *   ws: pp_multiorder_split_ws_bytes(n_types).
+ * pp_multiorder_concat: n_pieces layer pieces in part order -> the layer's global arrays.  HOST arrays [n_pieces] of DEVICE pointers (as
+ *   pp_adam_f32 takes its tensors) row_ptr (rows[k] entries are read: offsets into the piece's own edges), col, weight, last (edges[k]
+ *   entries; `last` and last_out may be NULL: the top layer) and HOST arrays rows / edges.  row_ptr_out [sum rows + 1] = piece entry + the
+ *   edges of the pieces before, closed by the edge total; col_out / weight_out / last_out [sum edges] the pieces' arrays one after another.
+ *   A piece without edges has rows[k] empty rows; all its arrays, row_ptr included, may be NULL.  No staging copy; PP_ERR_TOO_LARGE at 2^31 - 16 rows or edges. */
+size_t pp_multiorder_split_ws_bytes(int64_t n_types);
+int pp_multiorder_split(int64_t n_types, const int32_t* tptr, const int32_t* ibase, int64_t budget, int64_t max_parts, int64_t* report,
+                        int32_t* tptr_out, int32_t* ibase_out, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_multiorder_concat(int n_pieces, const void* const* row_ptr, const void* const* col, const void* const* weight, const void* const* last,
+                         const int64_t* rows, const int64_t* edges, int32_t* row_ptr_out, int32_t* col_out, float* weight_out, int32_t* last_out,
+                         pp_stream_t stream);
 /* The same layers of OBSERVED WALKS: MultiOrderModel.from_path_data(paths, max_order >= 2, mode="propagation"),
  * src/pathpyG/core/multi_order_model.py:194-241, on the walk store of PathData.append_walks, src/pathpyG/core/path_data.py:126-159:
  * node_sequence [positions] int64 the first-order node of every walk position, dag_num_nodes [walks] int64 positions per walk (L_w >= 1),

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import sys
 import threading
 from typing import NamedTuple
 
@@ -926,14 +927,20 @@ class MultiOrderLayer:
 
 
 def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delta, weight: torch.Tensor | None, max_order: int,
-                         clock: list | None = None, event_graph: torch.Tensor | None = None):
+                         clock: list | None = None, event_graph: torch.Tensor | None = None, pass_instances: int = _INT32_ROWS,
+                         passes: list | None = None):
     """All De Bruijn layers 1..max_order of a TIME-SORTED event stream, level by level (pp_multiorder_prepare / _step, csrc/pp_multiorder.hip):
     no instance graph ``[2, E_k]``, no per-instance node sequences, no global sort beyond the two of the first order; one read-back per order.
-    Returns ``[MultiOrderLayer]`` (index k - 1 = layer k; ``n_instances`` = E_k, the instance edges the reference would have lifted) or ``None``
-    when the generic kernels have to take over: a layer without edges, a node sequence with more than 4096 continuations (dense contact
-    streams), 2^31 or more instances at some order, an unsorted stream.  ``clock``: a list that receives one ``(name, start event, end event)``
-    per phase — the windows and level 1 ("prepare"), then every step ("layer k") — for measurements (bench.py).  ``event_graph``: a given
-    ``lift_order_temporal(g, delta)`` ([2, E2] int64, sorted by source) instead of ``time`` / ``delta`` (pp_multiorder_prepare_graph)."""
+    Returns ``[MultiOrderLayer]`` (index k - 1 = layer k; ``n_instances`` = E_k, the instance edges the reference would have lifted, a Python
+    int of any size) or ``None`` when the generic kernels have to take over: a layer without edges, a node sequence with more than 4096
+    continuations (dense contact streams), a layer with 2^31 - 16 or more edges, 2^31 continuations of one first-order node pair, an
+    unsorted stream.  A level with more than ``pass_instances`` instances (at most and by default what one step numbers, 2^31 - 17) is no refusal: from there
+    on every level is cut into parts of whole types of at most that many instances, the unchanged step runs on one part after another and
+    the parts' pieces are joined (``core/multi_order_passes.py``: pp_multiorder_split / _concat; one read-back per part and step, one per
+    split).  ``passes``: a list that receives the number of parts layer 1..max_order were built in (all ones without such a level).
+    ``clock``: a list that receives one ``(name, start event, end event)`` per phase — the windows and level 1 ("prepare"), then every
+    step ("layer k", one per part; in passes also "split k" and "concat k") — for measurements (bench.py).  ``event_graph``: a given ``lift_order_temporal(g, delta)`` ([2, E2]
+    int64, sorted by source) instead of ``time`` / ``delta`` (pp_multiorder_prepare_graph)."""
     ei = _edge_index(edge_index)
     dev = require_device(ei, time, weight, event_graph)
 
@@ -995,9 +1002,22 @@ def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
                                 weight=w, tlast=tlast)
         layers = [MultiOrderLayer(n_nodes=n, n_edges=types, n_instances=m, row_ptr=row_ptr, col=tlast[:types], weight=w[:types], last=tlast[:types])]
         cand_ptr, cand_last = row_ptr, tlast
+        budget = max(1, min(int(pass_instances), _INT32_ROWS - 1))    # (a step numbers at most _INT32_ROWS - 1 children)
+        if passes is not None:
+            passes[:] = [1] * max_order
         for k in range(2, max_order + 1):
-            if level.types == 0 or level.children == 0 or level.children >= _INT32_ROWS:
+            if level.types == 0 or level.children == 0:
                 return None
+            if level.children > budget:
+                # more instances than one step numbers (or than the caller's budget): the rest of the model in passes over ranges of types
+                from .core import multi_order_passes
+                built = multi_order_passes.continue_in_passes(sys.modules[__name__], level, cand_ptr, cand_last, tab, layers, max_order,
+                                                              weight is not None, budget, clock)
+                if built is None:
+                    return None
+                if passes is not None:
+                    passes[k - 1:] = built[1]
+                return built[0]
             last = k == max_order
             nxt = _multi_order_step(level, cand_ptr, cand_last, tab, weight is not None, last, clock, f"layer {k}")
             if nxt.status & 4:
@@ -1142,6 +1162,86 @@ def _multi_order_step(level: MultiOrderLevel, cand_ptr, cand_last, tab, weighted
             tlast_next = tlast_next[:new_types].clone()
     return MultiOrderLevel(types=new_types, children=new_children, status=status, tptr=tptr_next, ibase=ibase_next, inst=child, row_ptr=row_next,
                            col=col_next, weight=w_next, tlast=tlast_next)
+
+
+SPLIT_MAX_PARTS = 65536            # kMoSplitMaxParts of csrc/pp_multiorder.hip: parts one pp_multiorder_split makes
+
+
+def multi_order_split(level: MultiOrderLevel, budget: int) -> "list[MultiOrderLevel] | None":
+    """``level`` cut into parts of whole types with at most ``budget`` children each (pp_multiorder_split; one read-back): a part that starts
+    at type t0 ends before the first type whose children would take it past the budget, holds at least one type, and a single type above
+    the budget is a part of its own.  ``level.ibase`` may be wrapped (``level.children`` >= 2^31, the true count from the step's read-back):
+    the per-type counts are its unsigned differences, their prefix is int64.  Every part is a :class:`MultiOrderLevel` that
+    :func:`multi_order_step` takes as it is: ``tptr`` / ``ibase`` numbered from 0, ``inst`` / ``col`` / ``tlast`` / ``weight`` VIEWS of the
+    level's arrays, ``children`` a Python int, ``row_ptr`` None.  ``None``: a single type with 2^31 or more children.  ``ValueError``: a
+    budget so small that the level may need more than ``SPLIT_MAX_PARTS`` parts.  ``HipError``: ``ibase`` is not the (low 32 bits of the)
+    prefix of ``level.children`` counts below 2^31."""
+    dev = level.tptr.device
+    types, children, budget = int(level.types), int(level.children), int(budget)
+    if types <= 0 or budget < 1:
+        raise ValueError("multi_order_split: a level with types and a budget >= 1")
+    cap = min(types, 2 * (children // budget) + 2)         # (two neighbouring parts together exceed the budget)
+    if cap > SPLIT_MAX_PARTS:
+        raise ValueError(f"multi_order_split: {children} instances in parts of {budget} may need {cap} parts; one split makes at most {SPLIT_MAX_PARTS} "
+                         "(its cuts are walked one after another: it is meant for two to a few hundred parts) — raise the budget")
+    L = lib()
+    with torch.cuda.device(dev):
+        report = torch.empty(4 + 3 * (cap + 1), dtype=torch.int64, device=dev)
+        tptr = torch.empty(types + cap, dtype=torch.int32, device=dev)
+        ibase = torch.empty(types + cap, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pp_multiorder_split_ws_bytes(types), dev)
+        check(L.pp_multiorder_split(types, _p(level.tptr), _p(level.ibase), budget, cap, _p(report), _p(tptr), _p(ibase), _p(ws), ws.numel(), _stream()),
+              "pp_multiorder_split")
+        host = report.tolist()
+    parts, status, total = host[0], host[1], host[2]
+    if status & 2:
+        return None
+    if status or total != children or not 1 <= parts <= cap:
+        raise HipError(f"pp_multiorder_split: status {status}, {parts} parts (room for {cap}), {total} children counted, {children} expected")
+    cut_type, cut_child, cut_inst = (host[4 + r * (cap + 1): 4 + r * (cap + 1) + parts + 1] for r in range(3))
+    out = []
+    for p in range(parts):
+        t0, t1, i0, i1, at = cut_type[p], cut_type[p + 1], cut_inst[p], cut_inst[p + 1], cut_type[p] + p
+        out.append(MultiOrderLevel(types=t1 - t0, children=cut_child[p + 1] - cut_child[p], status=0, tptr=tptr[at: at + t1 - t0 + 1],
+                                   ibase=ibase[at: at + t1 - t0 + 1], inst=level.inst[i0:i1], row_ptr=None, col=level.col[t0:t1],
+                                   weight=None if level.weight is None else level.weight[t0:t1],
+                                   tlast=None if level.tlast is None else level.tlast[t0:t1]))
+    return out
+
+
+def multi_order_concat(pieces: list, want_last: bool):
+    """The layer pieces of a level's parts, in part order, joined into the layer's global arrays (pp_multiorder_concat, no read-back):
+    ``pieces`` = ``[(rows, level)]`` with ``level`` what :func:`multi_order_step` returned for the part of ``rows`` types (``row_ptr`` =
+    offsets into its own edges, ``col`` / ``weight`` / ``tlast`` of ``level.types`` edges) or ``None`` for a part without children: ``rows``
+    empty rows.  Returns ``(row_ptr int32 [sum rows + 1], col int32, weight float32, last int32 or None)``; ``want_last`` False: the top layer.
+    ``ValueError`` / ``HipError``: a layer with 2^31 or more rows or edges."""
+    filled = [b for _, b in pieces if b is not None]
+    if not filled:
+        raise ValueError("multi_order_concat: no piece with edges")
+    dev = filled[0].row_ptr.device
+    k = len(pieces)
+    rows, edges = [int(r) for r, _ in pieces], [0 if b is None else int(b.types) for _, b in pieces]
+    n_rows, n_edges = sum(rows), sum(edges)
+    ptrs = ctypes.c_void_p * k
+
+    def table(get):
+        return ptrs(*[(get(b).data_ptr() if e else None) for e, (_, b) in zip(edges, pieces)])
+    with torch.cuda.device(dev):
+        row_ptr = torch.empty(n_rows + 1, dtype=torch.int32, device=dev)
+        col = torch.empty(n_edges, dtype=torch.int32, device=dev)
+        weight = torch.empty(n_edges, dtype=torch.float32, device=dev)
+        last = torch.empty(n_edges, dtype=torch.int32, device=dev) if want_last else None
+        for r, b in pieces:
+            if b is None:
+                continue
+            if b.row_ptr.dtype != torch.int32 or b.row_ptr.numel() < r or (b.types and (b.col.dtype != torch.int32 or b.weight.dtype != torch.float32
+                                                                 or b.col.numel() < b.types or b.weight.numel() < b.types
+                                                                 or (want_last and b.tlast.numel() < b.types))):
+                raise ValueError("multi_order_concat: a piece's arrays are not int32 / float32 of its sizes")
+        check(lib().pp_multiorder_concat(k, ptrs(*[(None if b is None else b.row_ptr.data_ptr()) for _, b in pieces]), table(lambda b: b.col), table(lambda b: b.weight),
+                                         table(lambda b: b.tlast) if want_last else None, (ctypes.c_int64 * k)(*rows), (ctypes.c_int64 * k)(*edges),
+                                         _p(row_ptr), _p(col), _p(weight), _p(last), _stream()), "pp_multiorder_concat")
+    return row_ptr, col, weight, last
 
 
 def multi_order_node_loads(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delta, weight: torch.Tensor | None = None):

@@ -766,6 +766,8 @@ def _second_order_fused(g: TemporalGraph, delta, weight: str, cached: bool):
 
 LARGE_HUB_EVENTS = 65536
 LIFT_ONLY_ORDER2 = False     # from_temporal_graph(max_order=2) on a stream with a node of LARGE_HUB_EVENTS events: True = the level-by-level builder (no GCN plans)
+_INT32_ROWS = _hip._INT32_ROWS    # instances one step of the level-by-level builder numbers, and rows the generic kernels' int32 arrays hold
+PASS_INSTANCES = _INT32_ROWS      # from_temporal_graph(max_order >= 3): a level with more instances than this (and any level one step cannot number) is built in passes over ranges of its types (core/multi_order_passes.py); smaller = less memory per step
 
 
 def _has_large_hub(g: TemporalGraph) -> bool:
@@ -789,8 +791,11 @@ def _multi_order_fused(g: TemporalGraph, delta, max_order: int, weight: str, cac
     layer comes out as source-major CSR with merged weights, the reference's layer tensors are deferred views of it (:func:`_csr_layers`), the
     ``inverse_idx`` of the layers from 3 on comes from the generic kernels (:func:`_generic_inverses`).
     ``event_graph``: a given ``lift_order_temporal(g, delta)`` — its edges are the continuation windows (``pp_multiorder_prepare_graph``).
+    A level with more than ``PASS_INSTANCES`` instances (default: 2^31 - 16; one step numbers one less) is built in passes over ranges of its types
+    (``core/multi_order_passes.py``); ``sizes["passes"]`` holds the number of parts per layer — all ones when no level reached the budget —
+    and ``sizes["layers"]`` the true instance counts as Python ints.
     ``None``: the builder does not apply (see :func:`_fast_stream`; a layer without edges, a node sequence with more than 4096 continuations,
-    2^31 instances, an event graph that is not sorted by source)."""
+    a layer with 2^31 - 16 or more edges, an event graph that is not sorted by source)."""
     stream = _fast_stream(g, weight)
     if stream is None:
         return None
@@ -799,24 +804,39 @@ def _multi_order_fused(g: TemporalGraph, delta, max_order: int, weight: str, cac
         event_graph = _dispatch.plain(event_graph)
         if not isinstance(event_graph, torch.Tensor) or not event_graph.is_cuda or event_graph.dim() != 2 or event_graph.size(0) != 2:
             return None
-    built = _hip.multi_order_temporal(ei, time, n, delta, w, max_order, event_graph=event_graph)
+    passes: list = []
+    built = _hip.multi_order_temporal(ei, time, n, delta, w, max_order, event_graph=event_graph, pass_instances=PASS_INSTANCES, passes=passes)
     if built is None:
         return None
     out = MultiOrderModel()
-    out.sizes = {"m": m, "N": n, "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in built]}
-    out.layers = _csr_layers(g, ei, built, cached, inverse_high=_generic_inverses(g, delta, max_order, weight, cached, event_graph))
+    out.sizes = {"m": m, "N": n, "layers": [(b.n_nodes, b.n_edges, b.n_instances) for b in built], "passes": passes}
+    out.layers = _csr_layers(g, ei, built, cached, inverse_high=_generic_inverses(g, delta, max_order, weight, cached, event_graph,
+                                                                                  instances=[b.n_instances for b in built]))
     return out
 
 
-def _generic_inverses(g: TemporalGraph, delta, max_order: int, weight: str, cached: bool, event_graph):
+def _generic_inverses(g: TemporalGraph, delta, max_order: int, weight: str, cached: bool, event_graph, instances=None):
     """``k -> inverse_idx`` of the layers from 3 on of a level-by-level model.  It numbers the reference's order-k INSTANCES (edges of the
     order-(k-1) instance graph, lexicographic), which only the generic kernels make: ONE generic build of the same layers, on first use,
-    serves every layer of the model (one per layer would run K - 2 of them); only its inverse maps are kept."""
+    serves every layer of the model (one per layer would run K - 2 of them); only its inverse maps are kept.
+    ``instances``: the instance counts of the layers 1.. (``sizes["layers"]``'s third entries).  The generic kernels hold fewer than
+    ``_INT32_ROWS`` instances per order, a model built in passes may have more: the shared build stops at the highest order below the
+    limit, and reading ``inverse_idx`` of a layer at or beyond the first order that reaches it raises ``RuntimeError`` instead of starting
+    a build that cannot succeed.  Nothing is decided before the first read: ``Graph.to``, ``MultiOrderModel.to`` and pickling keep the value
+    deferred."""
     kept = {}
 
     def inverse_of(k):
+        reach = max_order
+        for j, count in enumerate(instances or (), start=1):
+            if count >= _INT32_ROWS:
+                reach = min(reach, j - 1)
+                break
+        if k > reach:
+            raise RuntimeError(f"inverse_idx of layer {k}: layer {reach + 1} has {instances[reach]} instances, and the generic kernels that number "
+                               f"a layer's instances hold fewer than {_INT32_ROWS} (2^31 - 16) of them")
         if not kept:
-            model = MultiOrderModel._from_temporal_graph_generic(g, delta, max_order, weight, cached, event_graph)
+            model = MultiOrderModel._from_temporal_graph_generic(g, delta, reach, weight, cached, event_graph)
             kept.update((j, layer.data.inverse_idx) for j, layer in model.layers.items() if j >= 3)
         return kept[k]
 

@@ -1288,6 +1288,130 @@ static MoPathInvWs carve_mo_path_inv(void* ws, int64_t walks) {
     return w;
 }
 
+// ------------------------------------------------------------------ a level in PASSES: contiguous ranges of its types, one after another
+// The children of a type depend on that type's instances only, instance records point into the global `tab`, columns are positions in the
+// global candidate tables: any contiguous range of a level's types with tptr / ibase renumbered from 0 is an input of the unchanged
+// pp_multiorder_step (what a rank of the split by first node is given).  One GPU takes the ranges one after another when the level's
+// children do not fit int32 ids (or a budget of the caller's): pp_multiorder_split cuts a level, pp_multiorder_concat joins the parts' layer
+// pieces.  A level with 2^31 or more children has a WRAPPED int32 ibase (the scan adds in int64 and stores the low 32 bits); every single
+// count is below 2^31 (k_mo_sums1* / mo_children_count clamp and set kMoOverflow, which the caller has checked), so the unsigned difference
+// of neighbouring entries is the true count.
+constexpr int64_t kMoSplitParts = 1, kMoSplitType = 2, kMoSplitBase = 4;     // status bits of pp_multiorder_split
+constexpr int64_t kMoRows = 0x7ffffff0;                                      // what the int32 arrays of a step hold
+constexpr int64_t kMoSplitMaxParts = 65536;                                  // parts of one split: the cuts are walked by ONE lane (k_mo_split_cuts)
+
+__global__ __launch_bounds__(kBlock) void k_mo_split_counts(const int32_t* __restrict__ ibase, int64_t n_types, int32_t* __restrict__ cnt,
+                                                           int64_t* __restrict__ status) {
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n_types) return;
+    uint32_t c = (uint32_t)ibase[t + 1] - (uint32_t)ibase[t];
+    if (c > 0x7fffffffu) { atomicOr((unsigned long long*)status, (unsigned long long)kMoSplitBase); c = 0u; }
+    cnt[t] = (int32_t)c;
+}
+
+// The greedy cuts: a part that starts at type t0 ends before the first type t with prefix[t + 1] - prefix[t0] > budget, holds at least one
+// type, and a single type above the budget is a part of its own (kMoSplitType when it does not fit a step either).  Every cut depends on
+// the one before it: one lane, one bisection of the int64 prefix per part.  Meant for 2 .. a few hundred parts (a level of 2^31 .. 2^38
+// instances in passes of 2^30 .. 2^31); kMoSplitMaxParts bounds it (~30 dependent loads per part: about a second at the bound), a budget
+// that needs more parts is refused by the caller.
+// report: {parts, status, children of the level, largest part} and three rows [max_parts + 1]: first type, children before, instances before.
+__global__ void k_mo_split_cuts(const int64_t* __restrict__ prefix, const int32_t* __restrict__ tptr, int64_t n_types, int64_t budget, int64_t max_parts,
+                                int64_t* __restrict__ report) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    int64_t* cut_type = report + 4;
+    int64_t* cut_child = cut_type + (max_parts + 1);
+    int64_t* cut_inst = cut_child + (max_parts + 1);
+    int64_t status = report[1], parts = 0, largest = 0, t0 = 0;
+    cut_type[0] = 0; cut_child[0] = 0; cut_inst[0] = (int64_t)tptr[0];
+    while (t0 < n_types) {
+        if (parts == max_parts) { status |= kMoSplitParts; break; }
+        const int64_t target = prefix[t0] + budget;
+        int64_t lo = t0 + 1, hi = n_types + 1;               // first j in (t0, n_types] with prefix[j] > target, or n_types + 1
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (prefix[mid] > target) hi = mid; else lo = mid + 1;
+        }
+        int64_t end = lo - 1;                                 // type end = lo - 1 is the first that no longer fits
+        if (end <= t0) end = t0 + 1;
+        const int64_t mine = prefix[end] - prefix[t0];
+        if (mine >= kMoRows) status |= kMoSplitType;
+        if (mine > largest) largest = mine;
+        ++parts;
+        cut_type[parts] = end; cut_child[parts] = prefix[end]; cut_inst[parts] = (int64_t)tptr[end];
+        t0 = end;
+    }
+    report[0] = parts; report[1] = status; report[2] = prefix[n_types]; report[3] = largest;
+}
+
+// tptr / ibase of all parts, each numbered from 0: part p's [types_p + 1] entries start at entry cut_type[p] + p of the outputs
+__global__ __launch_bounds__(kBlock) void k_mo_split_rebase(const int64_t* __restrict__ prefix, const int32_t* __restrict__ tptr, int64_t n_types,
+                                                           int64_t max_parts, const int64_t* __restrict__ report, int32_t* __restrict__ tptr_out,
+                                                           int32_t* __restrict__ ibase_out) {
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t parts = report[0];
+    if (report[1] != 0 || parts < 1 || parts > max_parts || j >= n_types + parts) return;
+    const int64_t* cut_type = report + 4;
+    int64_t lo = 0, hi = parts;                               // last part whose first entry is at or before j
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (cut_type[mid] + mid <= j) lo = mid; else hi = mid;
+    }
+    const int64_t t = j - lo, first = cut_type[lo];           // first <= t <= cut_type[lo + 1] <= n_types
+    tptr_out[j] = tptr[t] - tptr[first];
+    ibase_out[j] = (int32_t)(prefix[t] - prefix[first]);      // (below kMoRows: status is 0)
+}
+
+struct MoSplitWs {
+    int32_t* cnt;
+    int64_t* prefix;
+    void* scratch;
+    size_t scratch_bytes, total_bytes;
+};
+static MoSplitWs carve_mo_split(void* ws, int64_t n_types) {
+    Arena a(ws, (size_t)-1);
+    MoSplitWs w;
+    w.cnt = a.take<int32_t>(n_types);
+    w.prefix = a.take<int64_t>(n_types + 1);
+    w.scratch_bytes = scan_ws_bytes(n_types + 1);
+    w.scratch = a.take<char>((int64_t)w.scratch_bytes);
+    w.total_bytes = a.used;
+    return w;
+}
+
+// The pieces of a layer (one per part, in part order) into the layer's global arrays: blockIdx.y = piece, blockIdx.x strides over its rows
+// and edges.  The table travels as a kernel argument (k_adam's way): no staging block, every entry is read once and written once.
+constexpr int kMoConcatPieces = 32;
+struct MoConcatTable {
+    const int32_t* row_ptr[kMoConcatPieces];
+    const int32_t* col[kMoConcatPieces];
+    const float* weight[kMoConcatPieces];
+    const int32_t* last[kMoConcatPieces];
+    int64_t rows[kMoConcatPieces], edges[kMoConcatPieces], row_lo[kMoConcatPieces], edge_lo[kMoConcatPieces];
+};
+__global__ __launch_bounds__(kBlock) void k_mo_concat(MoConcatTable t, int32_t* __restrict__ row_ptr_out, int32_t* __restrict__ col_out,
+                                                     float* __restrict__ weight_out, int32_t* __restrict__ last_out) {
+    const int k = blockIdx.y;
+    const int64_t rows = t.rows[k], edges = t.edges[k], row_lo = t.row_lo[k], edge_lo = t.edge_lo[k];
+    const int32_t* __restrict__ rp = t.row_ptr[k];
+    const int32_t* __restrict__ col = t.col[k];
+    const float* __restrict__ w = t.weight[k];
+    const int32_t* __restrict__ last = t.last[k];
+    const int64_t longest = rows > edges ? rows : edges;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < longest; i += (int64_t)gridDim.x * kBlock) {
+        if (i < rows) {
+            int64_t at = rp ? (int64_t)rp[i] : 0;            // (no row pointers: a piece of empty rows)
+            at = at < 0 ? 0 : (at > edges ? edges : at);      // (a piece's offsets stay inside the piece)
+            row_ptr_out[row_lo + i] = (int32_t)(edge_lo + at);
+        }
+        if (i < edges) {
+            col_out[edge_lo + i] = col[i];
+            weight_out[edge_lo + i] = w[i];
+            if (last_out) last_out[edge_lo + i] = last[i];
+        }
+    }
+}
+__global__ void k_mo_concat_end(int32_t* __restrict__ row_ptr_out, int64_t rows, int64_t edges) { row_ptr_out[rows] = (int32_t)edges; }
+
 }  // namespace pp
 
 using namespace pp;
@@ -1577,6 +1701,81 @@ int pp_multiorder_paths_inverse(int64_t level, int64_t n_types, int64_t n_instan
     }
     k_mo_path_inverse<<<(unsigned)ceil_div(n_instances, kBlock), kBlock, 0, st>>>(tptr, n_types, (const uint4*)inst, n_instances, edge_walk, m, skip, level,
                                                                                   inverse);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+/* see include/pathpyg_amd.h: a level cut into parts of whole types */
+size_t pp_multiorder_split_ws_bytes(int64_t n_types) { return carve_mo_split(nullptr, n_types).total_bytes; }
+
+int pp_multiorder_split(int64_t n_types, const int32_t* tptr, const int32_t* ibase, int64_t budget, int64_t max_parts, int64_t* report,
+                        int32_t* tptr_out, int32_t* ibase_out, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(n_types > 0 && n_types < kMoRows, PP_ERR_ARG, "pp_multiorder_split: 1 .. 2^31 - 17 types");
+    PP_REQUIRE(budget >= 1 && max_parts >= 1 && max_parts <= n_types && max_parts <= kMoSplitMaxParts, PP_ERR_ARG,
+               "pp_multiorder_split: budget >= 1 and 1 <= max_parts <= min(n_types, %lld)", (long long)kMoSplitMaxParts);
+    PP_REQUIRE(tptr && ibase && report && tptr_out && ibase_out, PP_ERR_ARG, "pp_multiorder_split: null array");
+    MoSplitWs p = carve_mo_split(ws, n_types);
+    PP_REQUIRE(ws_bytes >= p.total_bytes, PP_ERR_WORKSPACE, "pp_multiorder_split: workspace too small");
+    PP_HIP(hipMemsetAsync(report, 0, 4 * sizeof(int64_t), st));
+    k_mo_split_counts<<<(unsigned)ceil_div(n_types, kBlock), kBlock, 0, st>>>(ibase, n_types, p.cnt, report + 1);
+    PP_LAUNCH_CHECK();
+    const int rc = exclusive_scan<int32_t, int64_t>(p.cnt, n_types, p.prefix, true, nullptr, p.scratch, p.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_mo_split_cuts<<<1, 1, 0, st>>>(p.prefix, tptr, n_types, budget, max_parts, report);
+    PP_LAUNCH_CHECK();
+    k_mo_split_rebase<<<(unsigned)ceil_div(n_types + max_parts, kBlock), kBlock, 0, st>>>(p.prefix, tptr, n_types, max_parts, report, tptr_out, ibase_out);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+/* see include/pathpyg_amd.h: the parts' layer pieces joined into the layer's global arrays */
+int pp_multiorder_concat(int n_pieces, const void* const* row_ptr, const void* const* col, const void* const* weight, const void* const* last,
+                         const int64_t* rows, const int64_t* edges, int32_t* row_ptr_out, int32_t* col_out, float* weight_out, int32_t* last_out,
+                         pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(n_pieces >= 1 && row_ptr && col && weight && rows && edges && row_ptr_out, PP_ERR_ARG, "pp_multiorder_concat: no pieces or a null table");
+    PP_REQUIRE(last_out == nullptr || last != nullptr, PP_ERR_ARG, "pp_multiorder_concat: last_out without the pieces' last nodes");
+    int64_t total_rows = 0, total_edges = 0;
+    for (int k = 0; k < n_pieces; ++k) {
+        PP_REQUIRE(rows[k] >= 0 && edges[k] >= 0 && rows[k] < kMoRows && edges[k] < kMoRows, PP_ERR_ARG, "pp_multiorder_concat: piece %d: bad size", k);
+        PP_REQUIRE(edges[k] == 0 || (rows[k] > 0 && row_ptr[k] && col[k] && weight[k] && (last_out == nullptr || last[k])), PP_ERR_ARG,
+                   "pp_multiorder_concat: piece %d: edges without rows, or a null array", k);
+        total_rows += rows[k];
+        total_edges += edges[k];
+        PP_REQUIRE(total_rows < kMoRows && total_edges < kMoRows, PP_ERR_TOO_LARGE, "pp_multiorder_concat: a layer with 2^31 or more rows or edges");
+    }
+    PP_REQUIRE(total_edges == 0 || (col_out && weight_out), PP_ERR_ARG, "pp_multiorder_concat: null output");
+    int64_t row_lo = 0, edge_lo = 0;
+    for (int k = 0; k < n_pieces;) {
+        MoConcatTable t;
+        int cnt = 0;
+        int64_t longest = 0;
+        for (; k < n_pieces && cnt < kMoConcatPieces; ++k) {
+            if (rows[k] > 0) {
+                t.row_ptr[cnt] = (const int32_t*)row_ptr[k];
+                t.col[cnt] = edges[k] ? (const int32_t*)col[k] : nullptr;
+                t.weight[cnt] = edges[k] ? (const float*)weight[k] : nullptr;
+                t.last[cnt] = (edges[k] && last_out) ? (const int32_t*)last[k] : nullptr;
+                t.rows[cnt] = rows[k]; t.edges[cnt] = edges[k]; t.row_lo[cnt] = row_lo; t.edge_lo[cnt] = edge_lo;
+                const int64_t l = rows[k] > edges[k] ? rows[k] : edges[k];
+                if (l > longest) longest = l;
+                ++cnt;
+            }
+            row_lo += rows[k];
+            edge_lo += edges[k];
+        }
+        if (cnt == 0) continue;
+        for (int q = cnt; q < kMoConcatPieces; ++q) {
+            t.row_ptr[q] = nullptr; t.col[q] = nullptr; t.weight[q] = nullptr; t.last[q] = nullptr;
+            t.rows[q] = 0; t.edges[q] = 0; t.row_lo[q] = 0; t.edge_lo[q] = 0;
+        }
+        int64_t gx = ceil_div(longest, kBlock);
+        if (gx > 1024) gx = 1024;
+        k_mo_concat<<<dim3((unsigned)gx, (unsigned)cnt), kBlock, 0, st>>>(t, row_ptr_out, col_out, weight_out, last_out);
+        PP_LAUNCH_CHECK();
+    }
+    k_mo_concat_end<<<1, 1, 0, st>>>(row_ptr_out, total_rows, total_edges);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

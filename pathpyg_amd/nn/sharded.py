@@ -62,6 +62,9 @@ class HipOps:
     multi_order_prepare_range = staticmethod(_hip.multi_order_prepare_range)
     multi_order_step = staticmethod(_hip.multi_order_step)
     multi_order_stitch = staticmethod(_hip.multi_order_stitch)
+    # ---- a level in passes over ranges of its types (core/multi_order_passes.continue_in_passes)
+    multi_order_split = staticmethod(_hip.multi_order_split)
+    multi_order_concat = staticmethod(_hip.multi_order_concat)
 
     @staticmethod
     def group_rows(keys: torch.Tensor, num_rows: int):
