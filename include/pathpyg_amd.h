@@ -519,6 +519,20 @@ int pp_dropout_f32(const float* X, int64_t n_rows, int F, double p, int64_t seed
 int pp_dropout_act_backward_f32(const float* dY, const float* Ydrop, int64_t n_rows, int F, double p, int64_t seed, int64_t tag, int64_t row0,
                                 const int64_t* rows, int act, float* dpre, float* dbias, pp_stream_t stream);
 
+/* F.dropout of the DEFAULT one-hot features (torch.eye, core/multi_order_model.py:529-533; dropped at nn/dbgnn.py:132,136) without the
+ * identity: dropout keeps or drops only the diagonal of I, so dropout(I) W^T = diag(d) W^T with d[g] = the factor pp_dropout_f32 gives element
+ * (g, g) of an [n, n] matrix (hash index g * n + g; 0 or 1 / (1 - p)).  out[r,:] = X[r,:] * d[row0 + r] for an [n_rows, F] matrix whose rows are
+ * the rows row0 .. row0 + n_rows of that product (forward: X = W^T; backward: X = A_hat^T dpre, out = dW^T).  Any F; out may alias X. */
+int pp_dropout_diag_rows_f32(const float* X, int64_t n_rows, int F, int64_t n, double p, int64_t seed, int64_t tag, int64_t row0, float* out,
+                             pp_stream_t stream);
+/* The first GCN layer on those features (GCNConv + F.elu on dropout(torch.eye), nn/dbgnn.py:132-133,136-137; core/multi_order_model.py:529-533)
+ * with the factor inside the aggregation — pp_spmm_f32 (S = X, no hub rows) with d as above for rows 0 .. n:
+ *   where 1 (forward)   Y[r,:] = act( sum_p val[p] * d[idx[p]] * X[idx[p],:] + self_coef[r] * d[r] * X[r,:] + bias ),  X = W^T: no scaled copy
+ *   where 2 (backward)  Y[r,:] = d[r] * ( sum_p val[p] * X[idx[p],:] + self_coef[r] * X[r,:] ),  X = dpre over the transposed CSR, Y = dW^T
+ * F a multiple of 4 in [4, 256], 16-byte aligned rows, n_rows <= n; self_coef NULL = no self term. */
+int pp_spmm_diag_drop_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* X, int F, const float* self_coef,
+                          const float* bias, int act, int where, int64_t n, double p, int64_t seed, int64_t tag, float* Y, pp_stream_t stream);
+
 /* Weight gradient of a dense layer of the DBGNN (autograd of lin / lin1 / lin2 / GCNConv.lin, dbgnn.py:64,133,139,149):
  * dW[M,K] = dH[N,M]^T X[N,K] and, when db != NULL, db[M] = column sums of dH.  fp32 on the matrix cores
  * (v_mfma_f32_32x32x2_f32, operands read straight from the row-major inputs), deterministic two-stage reduction. */

@@ -1505,6 +1505,47 @@ def dropout(x: torch.Tensor, p: float, seed: int, tag: int, row0: int = 0, rows:
     return out
 
 
+def dropout_diag_rows(x: torch.Tensor, n: int, p: float, seed: int, tag: int, row0: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``x[r] * d[row0 + r]`` with ``d[g]`` the factor :func:`dropout` gives element ``(g, g)`` of an ``[n, n]`` matrix — what dropout of an
+    identity matrix leaves of ``I @ x`` (pp_dropout_diag_rows_f32); ``out`` may be ``x`` itself."""
+    dev = require_device(x)
+    if x.dim() != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise ValueError("dropout_diag_rows: a contiguous fp32 [n_rows, F] matrix expected")
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty_like(x)
+        elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+            raise ValueError("dropout_diag_rows: out must be a contiguous fp32 tensor of x's shape on x's device")
+        if x.size(1) > 0:
+            check(lib().pp_dropout_diag_rows_f32(_p(x), x.size(0), x.size(1), int(n), float(p), int(seed), int(tag), int(row0), _p(out), _stream()),
+                  "pp_dropout_diag_rows_f32")
+    return out
+
+
+def spmm_diag_drop_supported(f: int, heavy: HeavyRows | None) -> bool:
+    """Whether :func:`spmm_diag_drop` takes rows of width ``f`` over a CSR with these hub rows (none: the chunked pre-pass sums unscaled rows)."""
+    return f % 4 == 0 and 4 <= f <= 256 and (heavy is None or heavy.n_heavy == 0)
+
+
+def spmm_diag_drop(ptr, idx, val, n_rows: int, x: torch.Tensor, self_coef, bias, act: bool, where: int, n: int, p: float, seed: int,
+                   tag: int) -> torch.Tensor:
+    """:func:`spmm` with ``s = x`` and the dropout factors ``d`` of an ``[n, n]`` identity's diagonal inside the kernel (pp_spmm_diag_drop_f32):
+    ``where = 1`` scales every source row (``act(A diag(d) x + self_coef * d * x + bias)``), ``where = 2`` every output row."""
+    dev = require_device(x, bias)
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        raise TypeError("DBGNN kernels are fp32")
+    if where == 1 and x.size(0) < n:
+        raise ValueError("spmm_diag_drop: the source matrix must have the identity's n rows")
+    if bias is not None:
+        bias = bias.contiguous()
+    with torch.cuda.device(dev):
+        y = torch.empty((n_rows, x.size(1)), dtype=torch.float32, device=dev)
+        check(lib().pp_spmm_diag_drop_f32(_p(ptr), _p(idx), _p(val), n_rows, _p(x), x.size(1), _p(self_coef), _p(bias), 1 if act else 0, int(where),
+                                          int(n), float(p), int(seed), int(tag), _p(y), _stream()), "pp_spmm_diag_drop_f32")
+    return y
+
+
 def dropout_act_backward(dy: torch.Tensor, y_dropped: torch.Tensor | None, p: float, seed: int, tag: int, row0: int = 0,
                          rows: torch.Tensor | None = None, act: bool = True, want_dbias: bool = False):
     """``(dpre, dbias or None)``: backward of :func:`dropout` fused with the ELU backward of the activation underneath (``act``)."""

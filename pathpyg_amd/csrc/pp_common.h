@@ -231,6 +231,10 @@ __device__ __forceinline__ bool dropout_keep(int64_t row, int col, int width, ui
     x = (x >> 16) ^ x;
     return x >= threshold;
 }
+// dropout factor of the DIAGONAL element (g, g) of an [n, n] matrix (0 or 1 / (1 - p)): all that dropout leaves of an identity matrix
+__device__ __forceinline__ float dropout_diag_factor(int64_t g, int n, uint32_t key, uint32_t threshold, float scale) {
+    return dropout_keep(g, (int)g, n, key, threshold) ? scale : 0.f;
+}
 static inline uint32_t dropout_key(int64_t seed, int64_t tag) {
     return (uint32_t)(((uint64_t)seed * 0x9E3779B1ull + (uint64_t)tag * 0x85EBCA6Bull + 0x27D4EB2Full) & 0xFFFFFFFFull);
 }

@@ -208,11 +208,19 @@ __global__ __launch_bounds__(kBlock) void k_ptr_from_sorted_u32(const uint32_t* 
 // consecutive rows TOGETHER so that their index loads, and then their row gathers, are in flight at the same time.
 // The kLanes lanes of a row fetch up to kLanes (index, value) pairs with ONE coalesced load each and hand them round by
 // shuffle: no row gather ever waits for an index load of its own row (measured: 2.12 -> 1.77 ms on the 10^7-row graph).
-template <int kLanes, int kRows, bool kFull>       // kFull: F == kLanes * 4, every lane owns a live column block
+// kDiag (the default one-hot features under dropout, see pp_spmm_diag_drop_f32): X stands behind a dropped identity, whose diagonal factors
+// d[g] are a pure function of g.  1: every SOURCE row is scaled, Y = act(A diag(d) X + self_coef d X + bias) — the factor goes into the
+// coefficient as the lane loads its (index, value) pair, one hash per CSR entry; 2: every OUTPUT row is scaled in the store epilogue.
+struct DiagDrop {
+    uint32_t key, thr;
+    float scale;
+    int n;
+};
+template <int kLanes, int kRows, bool kFull, int kDiag = 0>       // kFull: F == kLanes * 4, every lane owns a live column block
 __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx, const float* __restrict__ val,
                                                    int64_t n_rows, const float* __restrict__ X, int F, const float* __restrict__ self_coef,
                                                    const float* __restrict__ S, const float* __restrict__ bias, int act, HeavyRows heavy,
-                                                   float* __restrict__ Y) {
+                                                   float* __restrict__ Y, DiagDrop dd = DiagDrop{0u, 0u, 1.f, 1}) {
     constexpr int kGroups = kBlock / kLanes;
     const int64_t r0 = ((int64_t)blockIdx.x * kGroups + threadIdx.x / kLanes) * kRows;
     const int lane = threadIdx.x % kLanes;
@@ -244,6 +252,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
             const int mine = p0[q] + lane;
             my_j[q] = mine < p1[q] ? idx[mine] : 0;
             my_v[q] = mine < p1[q] ? (val ? val[mine] : 1.f) : 0.f;
+            if (kDiag == 1) my_v[q] *= dropout_diag_factor(my_j[q], dd.n, dd.key, dd.thr, dd.scale);
         }
         float4 self_row[kRows];
         float self_c[kRows];
@@ -251,6 +260,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
         for (int q = 0; q < kRows; ++q) {
             const bool live = self_coef != nullptr && r0 + q < n_rows;
             self_c[q] = live ? self_coef[r0 + q] : 0.f;
+            if (kDiag == 1 && live) self_c[q] *= dropout_diag_factor(r0 + q, dd.n, dd.key, dd.thr, dd.scale);
             self_row[q] = (live && col_live) ? *(const float4*)(S + (r0 + q) * F + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
@@ -260,6 +270,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
                     const int mine = base + lane;
                     my_j[q] = mine < p1[q] ? idx[mine] : 0;
                     my_v[q] = mine < p1[q] ? (val ? val[mine] : 1.f) : 0.f;
+                    if (kDiag == 1) my_v[q] *= dropout_diag_factor(my_j[q], dd.n, dd.key, dd.thr, dd.scale);
                 }
                 const int cnt = p1[q] - base < kLanes ? p1[q] - base : kLanes;
                 for (int e = 0; e < cnt; e += 4) {
@@ -289,6 +300,10 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
             o.x += self_c[q] * self_row[q].x + b.x; o.y += self_c[q] * self_row[q].y + b.y;
             o.z += self_c[q] * self_row[q].z + b.z; o.w += self_c[q] * self_row[q].w + b.w;
             if (act) o = elu_fast4(o);
+            if (kDiag == 2) {
+                const float d = dropout_diag_factor(r0 + q, dd.n, dd.key, dd.thr, dd.scale);
+                o.x *= d; o.y *= d; o.z *= d; o.w *= d;
+            }
             *(float4*)(Y + (r0 + q) * F + c0) = o;
         }
     }
@@ -397,6 +412,27 @@ __global__ __launch_bounds__(kBlock) void k_dropout(const float* __restrict__ X,
         const int c = (int)(i - r * F);
         const int64_t gr = rows ? rows[r] : row0 + r;
         out[i] = dropout_keep(gr, c, F, key, threshold) ? X[i] * scale : 0.f;
+    }
+}
+
+// out[r, :] = X[r, :] * d[row0 + r], d[g] = dropout factor of element (g, g) of an [n, n] matrix: dropout of the identity keeps or drops only
+// its diagonal, so dropout(I) W^T is this row scaling of W^T (and its gradient the same scaling of A_hat^T dpre).  out may alias X (each
+// thread reads the piece it writes).  kVec: one float4 per thread step (F % 4 == 0, 16-byte aligned rows); else one float.
+template <bool kVec>
+__global__ __launch_bounds__(kBlock) void k_dropout_diag_rows(const float* X, int64_t n_rows, int F, int n, uint32_t key, uint32_t threshold,
+                                                             float scale, int64_t row0, float* out) {
+    const int per_row = kVec ? F / 4 : F;
+    const int64_t total = n_rows * (int64_t)per_row;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t r = i / per_row;
+        const float d = dropout_diag_factor(row0 + r, n, key, threshold, scale);
+        if (kVec) {
+            float4 v = *(const float4*)(X + i * 4);
+            v.x *= d; v.y *= d; v.z *= d; v.w *= d;
+            *(float4*)(out + i * 4) = v;
+        } else {
+            out[i] = X[i] * d;
+        }
     }
 }
 
@@ -674,6 +710,36 @@ static int launch_spmm(const int32_t* ptr, const int32_t* idx, const float* val,
     return PP_OK;
 }
 
+// the float4 kernels with a diagonal dropout factor (where = 1: on the source rows, 2: on the output rows); F % 4 == 0, F <= 256, no hub rows
+static int launch_spmm_diag(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* X, int F, const float* self_coef,
+                            const float* S, const float* bias, int act, int where, DiagDrop dd, float* Y, hipStream_t st) {
+    if (n_rows == 0 || F == 0) return PP_OK;
+    const HeavyRows none{nullptr, nullptr};
+#define PP_SPMM_D4(L, FULL)                                                                                                                   \
+    do {                                                                                                                                      \
+        if (where == 1) k_spmm_v4<L, 2, FULL, 1><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd);  \
+        else k_spmm_v4<L, 2, FULL, 2><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd);             \
+    } while (0)
+#define PP_SPMM_D(L)                                                                  \
+    do {                                                                              \
+        const unsigned grid = (unsigned)ceil_div(n_rows, (kBlock / L) * 2);           \
+        if (F == L * 4) PP_SPMM_D4(L, true);                                          \
+        else PP_SPMM_D4(L, false);                                                    \
+    } while (0)
+    const int q = F / 4;
+    if (q <= 1) PP_SPMM_D(1);
+    else if (q <= 2) PP_SPMM_D(2);
+    else if (q <= 4) PP_SPMM_D(4);
+    else if (q <= 8) PP_SPMM_D(8);
+    else if (q <= 16) PP_SPMM_D(16);
+    else if (q <= 32) PP_SPMM_D(32);
+    else PP_SPMM_D(64);
+#undef PP_SPMM_D
+#undef PP_SPMM_D4
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
 // longest[0] / longest[1] = longest row of the destination-major / source-major CSR of a finished plan (zeroed by the caller)
 static int plan_longest_rows(const int32_t* in_ptr, int64_t n_dst, const int32_t* out_ptr, int64_t n_src, int64_t* longest, hipStream_t st) {
     if (n_dst > 0) {
@@ -848,6 +914,21 @@ int pp_spmm_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_
                        (hipStream_t)stream);
 }
 
+int pp_spmm_diag_drop_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* X, int F, const float* self_coef,
+                          const float* bias, int act, int where, int64_t n, double p, int64_t seed, int64_t tag, float* Y, pp_stream_t stream) {
+    PP_REQUIRE(n_rows >= 0, PP_ERR_ARG, "pp_spmm_diag_drop_f32: negative size");
+    PP_REQUIRE(F >= 4 && F % 4 == 0 && F <= 256, PP_ERR_ARG, "pp_spmm_diag_drop_f32: F must be a multiple of 4 in [4, 256]");
+    PP_REQUIRE(((uintptr_t)X | (uintptr_t)Y | (uintptr_t)bias) % 16 == 0, PP_ERR_ARG, "pp_spmm_diag_drop_f32: 16-byte alignment");
+    PP_REQUIRE(act == 0 || act == 1, PP_ERR_ARG, "pp_spmm_diag_drop_f32: act must be 0 (none) or 1 (elu)");
+    PP_REQUIRE(where == 1 || (where == 2 && act == 0 && bias == nullptr), PP_ERR_ARG,
+               "pp_spmm_diag_drop_f32: where must be 1 (source rows) or 2 (output rows; then without bias and activation)");
+    PP_REQUIRE(p >= 0.0 && p < 1.0, PP_ERR_ARG, "pp_spmm_diag_drop_f32: p must lie in [0, 1)");
+    PP_REQUIRE(n >= 1 && n < (int64_t)0x7fffffff && n_rows <= n, PP_ERR_ARG, "pp_spmm_diag_drop_f32: need n_rows <= n < 2^31");
+    const DropSite d = drop_site(p, seed, tag, 0);
+    return launch_spmm_diag(ptr, idx, val, n_rows, X, F, self_coef, self_coef ? X : nullptr, bias, act, where, DiagDrop{d.key, d.thr, d.scale, (int)n}, Y,
+                            (hipStream_t)stream);
+}
+
 // out_max[0] = max_r (ptr[r+1] - ptr[r]) of a CSR row-pointer array (device int64): does the plan have hub rows?
 int pp_max_row_length_i32(const int32_t* ptr, int64_t n_rows, int64_t* out_max, pp_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
@@ -1013,6 +1094,26 @@ int pp_dropout_f32(const float* X, int64_t n_rows, int F, double p, int64_t seed
     int64_t g = ceil_div(total, kBlock * 8);
     if (g > kMaxGrid) g = kMaxGrid;
     k_dropout<<<(unsigned)g, kBlock, 0, st>>>(X, n_rows, F, dropout_key(seed, tag), (uint32_t)(p * 4294967296.0), (float)(1.0 / (1.0 - p)), row0, rows, out);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_dropout_diag_rows_f32(const float* X, int64_t n_rows, int F, int64_t n, double p, int64_t seed, int64_t tag, int64_t row0, float* out,
+                             pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(n_rows >= 0 && F >= 1, PP_ERR_ARG, "pp_dropout_diag_rows_f32: bad shape");
+    PP_REQUIRE(p >= 0.0 && p < 1.0, PP_ERR_ARG, "pp_dropout_diag_rows_f32: p must lie in [0, 1)");
+    PP_REQUIRE(n >= 1 && n < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_dropout_diag_rows_f32: n must lie in [1, 2^31)");
+    PP_REQUIRE(row0 >= 0 && row0 + n_rows <= n, PP_ERR_ARG, "pp_dropout_diag_rows_f32: rows row0 .. row0 + n_rows must lie in [0, n)");
+    PP_REQUIRE(n_rows == 0 || (X != nullptr && out != nullptr), PP_ERR_ARG, "pp_dropout_diag_rows_f32: null matrix");
+    if (n_rows == 0) return PP_OK;
+    const bool vec = (F % 4 == 0) && (((uintptr_t)X | (uintptr_t)out) % 16 == 0);
+    const int64_t total = n_rows * (int64_t)(vec ? F / 4 : F);
+    int64_t g = ceil_div(total, kBlock * (vec ? 2 : 8));
+    if (g > kMaxGrid) g = kMaxGrid;
+    const DropSite d = drop_site(p, seed, tag, row0);
+    if (vec) k_dropout_diag_rows<true><<<(unsigned)g, kBlock, 0, st>>>(X, n_rows, F, (int)n, d.key, d.thr, d.scale, row0, out);
+    else k_dropout_diag_rows<false><<<(unsigned)g, kBlock, 0, st>>>(X, n_rows, F, (int)n, d.key, d.thr, d.scale, row0, out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -55,6 +55,36 @@ def _made(value) -> "Lazy":
     return out
 
 
+class Identity(Lazy):
+    """The ``n x n`` identity matrix, deferred: the reference's default DBGNN features (``torch.eye``, src/pathpyG/core/multi_order_model.py:
+    529-533) as a stored fact instead of ``n * n`` floats.  ``DBGNN.forward`` reads ``W^T`` where it would multiply by this matrix and never
+    resolves it; reading the attribute (``data.x``) makes ``torch.eye(n, n, device=device)`` as for any :class:`Lazy`.  A device move or a copy
+    of an unresolved identity is an unresolved identity, and a pickle holds ``(n, device)``."""
+
+    __slots__ = ("n", "device")
+
+    def __init__(self, n: int, device=None):
+        self.n, self.device = int(n), torch.device("cpu" if device is None else device)
+        super().__init__(self._eye, (self.n, self.n))
+
+    def _eye(self):
+        return torch.eye(self.n, self.n, device=self.device)
+
+    def mapped(self, fn) -> "Lazy":
+        if self.value is not None:                      # made already: the moved / copied tensor is a tensor like any other
+            return super().mapped(fn)
+        # (the device of the mapped form is found on a 0 x 0 stand-in: a move changes it, a copy does not)
+        return Identity(self.n, fn(torch.empty((0, 0), device=self.device)).device)
+
+    def holds(self, current) -> bool:
+        """Whether ``current`` (what a bag stores now) still is this identity: the deferred object itself, or the tensor it resolved to, not
+        edited in place since (the rule for every :class:`Lazy`-derived fact: a replaced or edited tensor is just a tensor)."""
+        return current is self or (self.value is not None and current is self.value and current._version == self.version)
+
+    def __reduce__(self):
+        return (Identity, (self.n, str(self.device)))
+
+
 def moved(value: Any, device) -> Any:
     """``value`` on ``device``: a tensor through ``.to``, a :class:`Lazy` as a deferred move (it stays deferred: moving a layer or a bundle must not
     materialise every [2, A2] index), anything else as it is."""
@@ -68,15 +98,37 @@ def moved(value: Any, device) -> Any:
 class Data:
     def __init__(self, **attrs: Any) -> None:
         object.__setattr__(self, "_store", {})
+        object.__setattr__(self, "_origin", {})         # key -> the Identity a stored tensor was resolved from (see is_identity)
         for key, value in attrs.items():
             self[key] = value
 
     def _resolved(self, key: str) -> Any:
         value = self._store[key]
         if isinstance(value, Lazy):
-            value = value.resolve()
-            self._store[key] = value
+            value = self._settle(key, value)
         return value
+
+    def _settle(self, key: str, lazy: Lazy) -> Any:
+        value = self._store[key] = lazy.resolve()
+        if isinstance(lazy, Identity):
+            self._origins()[key] = lazy
+        return value
+
+    def _origins(self) -> dict:
+        origin = self.__dict__.get("_origin")
+        if origin is None:                              # a bag restored from a pickle of an earlier version
+            origin = {}
+            object.__setattr__(self, "_origin", origin)
+        return origin
+
+    def is_identity(self, key: str) -> bool:
+        """Whether ``self[key]`` is an identity matrix BY CONSTRUCTION: a stored :class:`Identity`, still deferred or resolved to a tensor that
+        has been neither replaced nor edited in place since.  Answers without resolving (and without looking at any element)."""
+        value = self._store.get(key)
+        if isinstance(value, Identity):
+            return True
+        made = self._origins().get(key)
+        return made is not None and value is not None and made.holds(value)
 
     def peek(self, key: str) -> Any:
         """The stored object as it is (a :class:`Lazy` stays unresolved); ``None`` when absent."""
@@ -87,12 +139,14 @@ class Data:
         return self._resolved(key)
 
     def __setitem__(self, key: str, value: Any) -> None:
+        self._origins().pop(key, None)
         if value is None and key in self._store:
             del self._store[key]
         elif value is not None:
             self._store[key] = value
 
     def __delitem__(self, key: str) -> None:
+        self._origins().pop(key, None)
         del self._store[key]
 
     def __contains__(self, key: str) -> bool:
@@ -103,7 +157,7 @@ class Data:
         if key in store:
             value = store[key]
             if isinstance(value, Lazy):
-                value = store[key] = value.resolve()
+                value = self._settle(key, value)
             return value
         if key in _OPTIONAL:
             return None
@@ -116,7 +170,7 @@ class Data:
             self[key] = value
 
     def __delattr__(self, key: str) -> None:
-        del self._store[key]
+        del self[key]
 
     def keys(self) -> list[str]:
         return list(self._store.keys())
@@ -138,6 +192,8 @@ class Data:
         x = self._store.get("x")
         if isinstance(x, torch.Tensor):
             return x.size(0)
+        if isinstance(x, Identity):
+            return x.n
         ei = self._resolved("edge_index") if "edge_index" in self._store else None
         if isinstance(ei, torch.Tensor) and ei.numel() > 0:
             return int(ei.max()) + 1

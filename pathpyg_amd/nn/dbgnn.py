@@ -15,7 +15,8 @@ bias + ELU) is ONE hand-written kernel for layer widths 16/32/64/128/256 (``csrc
 the backward pass runs the same structure over the transposed CSR.  No library GEMM is called for ANY width: widths without a kernel of
 their own are zero-padded to the next kernel width (<= 256) or split into 256-wide blocks (:func:`dense_w`), and the reference's default
 one-hot features (``torch.eye``, multi_order_model.py:532-533) never meet a GEMM at all — ``I W^T`` is ``W^T``, the first layer is one CSR
-segment reduction over the rows of ``W^T``.  All tensors must live on the GPU; fp32 only.
+segment reduction over the rows of ``W^T`` (in training mode with dropout: of ``diag(d) W^T``, since dropout of the identity keeps or drops
+only its diagonal) and the identity itself is never made.  All tensors must live on the GPU; fp32 only.
 """
 from __future__ import annotations
 
@@ -320,6 +321,46 @@ class _DropAct(torch.autograd.Function):
         return dpre, dbias, None, None, None, None, None, None, None
 
 
+class _DiagDrop(torch.autograd.Function):
+    """``diag(d) x`` with ``d[r]`` the training-mode dropout factor of element ``(r, r)`` of an ``[n, n]`` matrix at a mask site (the very
+    decision ``pp_dropout_f32`` makes there): all that dropout of the default one-hot features leaves of ``dropout(I) W^T`` — a row scaling of
+    ``x = W^T`` (``pp_dropout_diag_rows_f32``).  A diagonal matrix is its own transpose: the backward pass scales the gradient the same way."""
+
+    @staticmethod
+    def forward(ctx, x, n: int, p: float, seed: int, tag: int, row0: int):
+        ctx.site = (n, p, seed, tag, row0)
+        return _hip.dropout_diag_rows(x.contiguous(), *ctx.site)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return _hip.dropout_diag_rows(d_out.contiguous(), *ctx.site), None, None, None, None, None
+
+
+class _OneHotDropLayer(torch.autograd.Function):
+    """``ELU(A_hat diag(d) W^T + b)`` — the first GCN layer on the default one-hot features in training mode with dropout, ``d`` as in
+    :class:`_DiagDrop` — with the factor applied INSIDE the aggregation: to every gathered row of ``x = W^T`` forward, in the store epilogue of
+    the transposed aggregation backward (``dW^T = diag(d) A_hat^T dpre``).  No scaled copy of ``W^T`` is written: 37-42 % less time than
+    :class:`_DiagDrop` around :class:`_Propagate`, which remains the route of widths off the float4 kernels and of plans
+    with hub rows.  Contract of ``_Propagate(grad_is_pre=True)``: the consumer hands back the gradient w.r.t. the pre-activation and computes
+    the bias gradient."""
+
+    @staticmethod
+    def supported(plan, width: int) -> bool:
+        return (plan.self_coef is not None and _hip.spmm_diag_drop_supported(width, plan.fwd_heavy)
+                and _hip.spmm_diag_drop_supported(width, plan.bwd_heavy))
+
+    @staticmethod
+    def forward(ctx, plan, x, bias, n: int, p: float, seed: int, tag: int):
+        ctx.plan, ctx.site = plan, (n, p, seed, tag)
+        return _hip.spmm_diag_drop(plan.fwd_ptr, plan.fwd_idx, plan.fwd_val, plan.n_dst, x, plan.self_coef, bias, True, 1, *ctx.site)
+
+    @staticmethod
+    def backward(ctx, dpre):
+        plan = ctx.plan
+        dx = _hip.spmm_diag_drop(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, plan.n_src, dpre.contiguous(), plan.self_coef, None, False, 2, *ctx.site)
+        return None, dx, None, None, None, None, None
+
+
 def _draw_seed() -> int:
     """One dropout seed per forward pass (from torch's CPU generator, so ``torch.manual_seed`` makes a run reproducible)."""
     return int(torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).item())
@@ -607,13 +648,15 @@ def _valid_plans(data):
     return rec["fo"], rec["ho"], rec["bi"]
 
 
-def _is_hinted_eye(data, name: str) -> bool:
-    """``data.x`` / ``data.x_h`` is the identity matrix ``MultiOrderModel.to_dbgnn_data`` created (its own stamp: assigning other features
-    later leaves the other hints alone)."""
-    hints = getattr(data, "_pp_hints", None) or {}
-    stamp = hints.get(name + "_eye")
-    t = getattr(data, name, None)
-    return stamp is not None and t is not None and stamp[0] is t and stamp[1] == t._version
+def _features(data, name: str, first_layer, n_nodes: int):
+    """The feature matrix ``data.x`` / ``data.x_h`` — or ``None`` where it is an identity matrix by construction (a
+    :class:`pathpyg_amd.data.Identity`, the default of ``MultiOrderModel.to_dbgnn_data``: still deferred, or read and neither replaced nor
+    edited in place since) over the graph's ``n_nodes`` nodes that fits the stack's first layer, which then reads ``W^T`` through the CSR.
+    Only the stored object is looked at: nothing is resolved (an identity of another size is made and multiplied like any matrix)."""
+    probe = getattr(data, "is_identity", None)
+    if probe is not None and probe(name) and int(data.peek(name).shape[0]) == first_layer.lin.weight.size(1) == n_nodes:
+        return None
+    return getattr(data, name)
 
 
 class GCNConv(Module):
@@ -680,8 +723,9 @@ class DBGNN(Module):
         self.lin = Linear(hidden_dims[-1], num_classes)
 
     def forward(self, data) -> torch.Tensor:
-        x, x_h = data.x, data.x_h
+        # (None: the default one-hot features, kept implicit)
         n_fo, n_ho = int(data.num_nodes), int(data.num_ho_nodes)
+        x, x_h = _features(data, "x", self.first_order_layers[0], n_fo), _features(data, "x_h", self.higher_order_layers[0], n_ho)
         # bundles made by MultiOrderModel.to_dbgnn_data carry hints (every Graph's edge index is row-sorted, the bipartite
         # sources are arange) that save three device round trips; foreign bundles are checked on the device instead
         handed = _valid_plans(data)
@@ -720,6 +764,16 @@ class DBGNN(Module):
                     weight = layer.lin.weight
                     site_in = (p, seed, tag + i, 0)
                     site_out = (p, seed, tag + i + 1 if i + 1 < len(layers) else out_tag, 0)
+                    if h is None:
+                        # the input is the identity: dropout(I) W^T = diag(d) W^T with d the factors of I's diagonal at this site, so the layer is
+                        # ELU(A_hat diag(d) W^T + b) — the one-hot reduction below over a row-scaled copy of W^T; backward: dW^T = diag(d) A_hat^T dpre
+                        if _OneHotDropLayer.supported(plan, weight.size(0)):
+                            h = _OneHotDropLayer.apply(plan, weight.t().contiguous(), layer.bias, weight.size(1), p, seed, tag + i)
+                        else:
+                            wt = _DiagDrop.apply(weight.t().contiguous(), weight.size(1), *site_in)
+                            h = _Propagate.apply(plan, wt, None, layer.bias, True, True)
+                        pending_bias, contract, applied = layer.bias, True, False
+                        continue
                     fused = _GcnLayer.supported(plan, h, weight)
                     in_kernel = fused and _hip.gcn_drop_supported(weight.size(1), weight.size(0))
                     if applied and in_kernel:
@@ -754,10 +808,10 @@ class DBGNN(Module):
 
         # No dropout between an activation and the dense layer that consumes it: every ELU backward is fused into the
         # epilogue of that dense layer's input-gradient GEMM (see _Dense / _Propagate.grad_is_pre).
-        def stack(layers, h, plan, one_hot=False):
+        def stack(layers, h, plan):
             below = None                                            # bias of the layer whose activation `h` is
             for i, layer in enumerate(layers):
-                if i == 0 and one_hot and h.size(0) == h.size(1) == layer.lin.weight.size(1):
+                if h is None:
                     # h is the identity (the reference's default features, multi_order_model.py:532-533): I W^T = W^T, so the layer is
                     # ELU(A_hat W^T + b) — one CSR segment reduction over the rows of W^T, no n x n matrix product; its backward pass
                     # (A_hat^T dpre) is the gradient of W^T
@@ -770,8 +824,8 @@ class DBGNN(Module):
                 below = layer.bias
             return h, below
 
-        x, bias_fo = stack(self.first_order_layers, x, plan_fo, _is_hinted_eye(data, "x"))
-        x_h, bias_ho = stack(self.higher_order_layers, x_h, plan_ho, _is_hinted_eye(data, "x_h"))
+        x, bias_fo = stack(self.first_order_layers, x, plan_fo)
+        x_h, bias_ho = stack(self.higher_order_layers, x_h, plan_ho)
         bl = self.bipartite_layer
         if plan_bi.fwd_val is None and x_h.size(1) % 4 == 0 and x_h.size(1) <= 256:
             # sum_j (W1 x_h[j] + b1) = W1 (sum_j x_h[j]) + deg * b1: aggregate the U higher-order rows FIRST (one gather pass over

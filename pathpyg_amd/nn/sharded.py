@@ -387,6 +387,22 @@ def dropout_mask(rows: torch.Tensor, width: int, p: float, seed: int, tag: int) 
     return (x >= int(p * 4294967296.0)).to(torch.float32) * (1.0 / (1.0 - p))
 
 
+def dropout_mask_diagonal(rows: torch.Tensor, n: int, p: float, seed: int, tag: int) -> torch.Tensor:
+    """``dropout_mask(rows, n, p, seed, tag)[i, rows[i]]`` without the ``[len(rows), n]`` matrix: the factor of the DIAGONAL element
+    ``(r, r)`` of an ``[n, n]`` matrix for every ``r`` in ``rows`` — all that dropout leaves of an identity matrix (the default one-hot
+    features), and the torch statement of ``pp_dropout_diag_rows_f32``.  Same hash on the index ``r * n + r`` (which passes 2^32 from
+    ``n`` = 65 536 on: both words of it enter)."""
+    m32 = 0xFFFFFFFF
+    r = rows.to(torch.int64)
+    idx = r * n + r
+    key = (seed * 0x9E3779B1 + tag * 0x85EBCA6B + 0x27D4EB2F) & m32
+    x = ((idx & m32) * 2654435761 + (idx >> 32) * 40503 + key) & m32
+    x = (((x >> 16) ^ x) * 0x45D9F3B) & m32
+    x = (((x >> 16) ^ x) * 0x45D9F3B) & m32
+    x = (x >> 16) ^ x
+    return (x >= int(p * 4294967296.0)).to(torch.float32) * (1.0 / (1.0 - p))
+
+
 class _ShardedGcnStack(torch.autograd.Function):
     """A stack of GCN layers ``h_{l+1} = ELU(A_hat h_l W_l^T + b_l)`` on this rank's destination rows.
 
