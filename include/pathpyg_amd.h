@@ -532,6 +532,18 @@ int pp_dropout_diag_rows_f32(const float* X, int64_t n_rows, int F, int64_t n, d
  * F a multiple of 4 in [4, 256], 16-byte aligned rows, n_rows <= n; self_coef NULL = no self term. */
 int pp_spmm_diag_drop_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* X, int F, const float* self_coef,
                           const float* bias, int act, int where, int64_t n, double p, int64_t seed, int64_t tag, float* Y, pp_stream_t stream);
+/* The same layer (nn/dbgnn.py:132-133,136-137 on the default features of core/multi_order_model.py:529-533) on ONE RANK's share of a
+ * destination-row partition: the CSR runs over LOCAL slots [owned | halo] and map[slot] (int64, distinct values in [0, n)) is the global id g,
+ * at which d[g] is hashed and the replicated matrix W^T [n, F] is addressed — no feature row is stored or exchanged for such a graph.
+ *   where 1 (forward)   Y[r,:] = act( sum_p val[p] * d[map[idx[p]]] * X[map[idx[p]],:] + self_coef[r] * d[map[r]] * X[map[r],:] + bias ),
+ *                       r < n_rows = n_self owned rows, X = W^T [n, F], Y [n_rows, F]
+ *   where 2 (backward)  Y[map[s],:] = d[map[s]] * ( sum_p val[p] * X[idx[p],:] + (s < n_self ? self_coef[s] * X[s,:] : 0) ),  s < n_rows local
+ *                       source slots over the transposed CSR, X = dpre [n_self, F], Y [n, F] = the rank's partial dW^T, zero-filled by the
+ *                       CALLER (rows of ids no slot maps to are not written); plain stores, the ids are distinct.
+ * CSR-entry order and additions are pp_spmm_diag_drop_f32's: with map = 0 .. n_rows the results are the same bits.  Conditions as there. */
+int pp_spmm_diag_drop_map_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, int64_t n_self, const float* X, int F,
+                              const float* self_coef, const float* bias, int act, int where, const int64_t* map, int64_t n, double p, int64_t seed,
+                              int64_t tag, float* Y, pp_stream_t stream);
 
 /* Weight gradient of a dense layer of the DBGNN (autograd of lin / lin1 / lin2 / GCNConv.lin, dbgnn.py:64,133,139,149):
  * dW[M,K] = dH[N,M]^T X[N,K] and, when db != NULL, db[M] = column sums of dH.  fp32 on the matrix cores
@@ -576,6 +588,15 @@ int pp_cross_entropy_f32(const float* logits, const int64_t* target, int64_t n, 
 size_t pp_cross_entropy_masked_ws_bytes(void);
 int pp_cross_entropy_masked_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
                                 int64_t ignore_index, int use_ignore, void* result, float* dlogits_raw, void* ws, size_t ws_bytes, pp_stream_t stream);
+/* The same pass for ONE RANK of a partitioned model (the tutorial loop of docs/tutorial/netzschleuder.ipynb cells 15-17 over rows that live on
+ * several GPUs): raw_sums = 32 bytes on the device, 8-byte aligned: double num, double den, int64 selected, int64 out of range — the sums
+ * BEFORE the rounding to fp32, so that the ranks' sums can be added (all-reduce) and rounded once.  dlogits_raw, ws as above. */
+int pp_cross_entropy_masked_sums_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
+                                     int64_t ignore_index, int use_ignore, void* raw_sums, float* dlogits_raw, void* ws, size_t ws_bytes,
+                                     pp_stream_t stream);
+/* ... and the finish on the reduced sums: sums [2] double {num, den}, counts [2] int64 {selected, out of range} -> result, the 32 bytes of
+ * pp_cross_entropy_masked_f32 with exactly its arithmetic (mean = (float)(num / den), inv_den = valid rows ? (float)(1 / den) : 0). */
+int pp_masked_finish_f32(const double* sums, const int64_t* counts, void* result, pp_stream_t stream);
 
 /* Confusion matrix of the predictions under the same selection: counts [C,C] int64 (zeroed by the callee), row = true class, column =
  * predicted class = the lowest column holding the row maximum, a NaN counting as the maximum (numpy's argmax).  status [1] int64 (zeroed by

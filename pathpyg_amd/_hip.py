@@ -1546,6 +1546,57 @@ def spmm_diag_drop(ptr, idx, val, n_rows: int, x: torch.Tensor, self_coef, bias,
     return y
 
 
+def _check_row_map(row_map: torch.Tensor, n: int) -> None:
+    """A row map addresses the replicated ``[n, F]`` matrix inside the kernel: its range is verified ONCE per tensor (and in-place version) —
+    one tiny reduction and a 16-byte read at the first use, nothing per step."""
+    key = (row_map._version, int(n))
+    if getattr(row_map, "_pp_map_range", None) == key:
+        return
+    if row_map.numel():
+        lo, hi = minmax(row_map)
+        if lo < 0 or hi >= n:
+            raise IndexError(f"spmm_diag_drop_map: the row map holds ids outside [0, {n}) ({lo} .. {hi})")
+    try:
+        row_map._pp_map_range = key
+    except Exception:
+        pass
+
+
+def spmm_diag_drop_map(ptr, idx, val, n_rows: int, x: torch.Tensor, self_coef, bias, act: bool, where: int, row_map: torch.Tensor, n: int,
+                       p: float, seed: int, tag: int, n_self: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`spmm_diag_drop` on one rank's rectangular share of the graph (pp_spmm_diag_drop_map_f32): the CSR runs over local slots and
+    ``row_map`` (int64, distinct global ids in ``[0, n)``, one per local source slot) says which row of the replicated ``[n, F]`` matrix a slot is.
+    ``where = 1``: ``x = W^T [n, F]``, result ``[n_rows, F]`` (``out``: written there); ``where = 2``: ``x = dpre [n_self, F]`` over the transposed
+    CSR of the ``n_rows`` source slots, result = the rank's partial ``dW^T [n, F]`` (rows no slot maps to are zero)."""
+    dev = require_device(x, bias, row_map)
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        raise TypeError("DBGNN kernels are fp32")
+    if row_map.dtype != torch.int64 or row_map.dim() != 1 or not row_map.is_contiguous():
+        raise ValueError("spmm_diag_drop_map: the row map must be a contiguous int64 vector")
+    n_self = n_rows if n_self is None else int(n_self)
+    if where == 1 and (x.size(0) != n or row_map.numel() < n_rows):
+        raise ValueError("spmm_diag_drop_map: where 1 needs the [n, F] matrix and a map entry for every local source slot")
+    if where == 2 and (x.size(0) != n_self or row_map.numel() != n_rows):
+        raise ValueError("spmm_diag_drop_map: where 2 needs dpre on the n_self owned rows and one map entry per source slot")
+    _check_row_map(row_map, n)
+    if bias is not None:
+        bias = bias.contiguous()
+    with torch.cuda.device(dev):
+        if where == 2:
+            y = torch.zeros((n, x.size(1)), dtype=torch.float32, device=dev)
+        elif out is not None:
+            if tuple(out.shape) != (n_rows, x.size(1)) or out.dtype != torch.float32 or not out.is_contiguous():
+                raise ValueError("spmm_diag_drop_map: out must be a contiguous fp32 [n_rows, F] tensor")
+            y = out
+        else:
+            y = torch.empty((n_rows, x.size(1)), dtype=torch.float32, device=dev)
+        check(lib().pp_spmm_diag_drop_map_f32(_p(ptr), _p(idx), _p(val), n_rows, n_self, _p(x), x.size(1), _p(self_coef), _p(bias), 1 if act else 0,
+                                              int(where), _p(row_map), int(n), float(p), int(seed), int(tag), _p(y), _stream()),
+              "pp_spmm_diag_drop_map_f32")
+    return y
+
+
 def dropout_act_backward(dy: torch.Tensor, y_dropped: torch.Tensor | None, p: float, seed: int, tag: int, row0: int = 0,
                          rows: torch.Tensor | None = None, act: bool = True, want_dbias: bool = False):
     """``(dpre, dbias or None)``: backward of :func:`dropout` fused with the ELU backward of the activation underneath (``act``)."""
@@ -1851,6 +1902,46 @@ def cross_entropy_masked(logits: torch.Tensor, target: torch.Tensor, mask: torch
                                             0 if ignore_index is None else 1, _p(result), _p(grad), _p(ws), ws.numel(), _stream()),
               "pp_cross_entropy_masked_f32")
     return MaskedSums(result[:2].view(torch.float32), result[2:]), grad
+
+
+class MaskedRawSums(NamedTuple):
+    """The 32-byte device result of pp_cross_entropy_masked_sums_f32, as two views of one buffer."""
+    sums: torch.Tensor        # float64 [2]: sum w[y] nll, sum w[y] — not yet rounded to fp32: a partitioned model adds its ranks' sums first
+    counts: torch.Tensor      # int64 [2]: selected rows, selected rows whose target lies outside [0, C)
+
+
+def cross_entropy_masked_sums(logits: torch.Tensor, target: torch.Tensor, mask: torch.Tensor | None = None, weight: torch.Tensor | None = None,
+                              ignore_index: int | None = None, want_grad: bool = True):
+    """:func:`cross_entropy_masked` for one rank of a partitioned model: ``(raw, raw_grad)`` with ``raw`` a :class:`MaskedRawSums` — the
+    float64 sums as they stand before :func:`masked_finish` — and the same ``raw_grad``.  An empty ``[0, C]`` share gives zero sums."""
+    dev = require_device(logits, target, mask, weight)
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError("cross_entropy_masked_sums: logits must be float32 [N, C]")
+    logits = logits.contiguous()
+    n, c = logits.shape
+    target, mask, weight = _selection("cross_entropy_masked_sums", n, c, target, mask, weight)
+    with torch.cuda.device(dev):
+        result = torch.empty(4, dtype=torch.int64, device=dev)
+        grad = torch.empty_like(logits) if want_grad else None
+        L = lib()
+        ws = _workspace(L.pp_cross_entropy_masked_ws_bytes(), dev)
+        check(L.pp_cross_entropy_masked_sums_f32(_p(logits), _p(target), _p(mask), _p(weight), n, c, 0 if ignore_index is None else int(ignore_index),
+                                                 0 if ignore_index is None else 1, _p(result), _p(grad), _p(ws), ws.numel(), _stream()),
+              "pp_cross_entropy_masked_sums_f32")
+    return MaskedRawSums(result[:2].view(torch.float64), result[2:]), grad
+
+
+def masked_finish(sums: torch.Tensor, counts: torch.Tensor) -> MaskedSums:
+    """float64 ``[2]`` sums and int64 ``[2]`` counts (a rank's, or the all-reduced ones) -> the :class:`MaskedSums` that
+    :func:`cross_entropy_masked` returns for the same sums (pp_masked_finish_f32: the same arithmetic)."""
+    dev = require_device(sums, counts)
+    if sums.dtype != torch.float64 or counts.dtype != torch.int64 or sums.numel() != 2 or counts.numel() != 2:
+        raise ValueError("masked_finish: float64 [2] sums and int64 [2] counts expected")
+    sums, counts = sums.contiguous(), counts.contiguous()
+    with torch.cuda.device(dev):
+        result = torch.empty(4, dtype=torch.int64, device=dev)
+        check(lib().pp_masked_finish_f32(_p(sums), _p(counts), _p(result), _stream()), "pp_masked_finish_f32")
+    return MaskedSums(result[:2].view(torch.float32), result[2:])
 
 
 def confusion(logits: torch.Tensor, target: torch.Tensor, mask: torch.Tensor | None = None, ignore_index: int | None = None,

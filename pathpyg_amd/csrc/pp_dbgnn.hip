@@ -216,11 +216,20 @@ struct DiagDrop {
     float scale;
     int n;
 };
-template <int kLanes, int kRows, bool kFull, int kDiag = 0>       // kFull: F == kLanes * 4, every lane owns a live column block
+// kMap (pp_spmm_diag_drop_map_f32: a rank's rectangular share of the graph, the identity's rows known by GLOBAL id): the rows of this CSR are
+// LOCAL slots and rm.map[slot] is the global id g, which is where d[g] is hashed and where the replicated [n, F] matrix is addressed —
+// 1: idx[p] and the self row go through the map as they are loaded (X = W^T has n rows; Y has the local rows); 2: the OUTPUT row goes through
+// the map (X = dpre and idx are local, the self term only exists for the rm.n_self owned rows; Y = this rank's partial dW^T, zero-filled by the
+// caller, slots have distinct ids: plain stores).  The order of the CSR entries and of the additions is the unmapped kernel's.
+struct RowMap {
+    const int64_t* map;
+    int64_t n_self;
+};
+template <int kLanes, int kRows, bool kFull, int kDiag = 0, bool kMap = false>       // kFull: F == kLanes * 4, every lane owns a live column block
 __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx, const float* __restrict__ val,
                                                    int64_t n_rows, const float* __restrict__ X, int F, const float* __restrict__ self_coef,
                                                    const float* __restrict__ S, const float* __restrict__ bias, int act, HeavyRows heavy,
-                                                   float* __restrict__ Y, DiagDrop dd = DiagDrop{0u, 0u, 1.f, 1}) {
+                                                   float* __restrict__ Y, DiagDrop dd = DiagDrop{0u, 0u, 1.f, 1}, RowMap rm = RowMap{nullptr, 0}) {
     constexpr int kGroups = kBlock / kLanes;
     const int64_t r0 = ((int64_t)blockIdx.x * kGroups + threadIdx.x / kLanes) * kRows;
     const int lane = threadIdx.x % kLanes;
@@ -251,6 +260,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
             }
             const int mine = p0[q] + lane;
             my_j[q] = mine < p1[q] ? idx[mine] : 0;
+            if (kMap && kDiag == 1) my_j[q] = mine < p1[q] ? (int)rm.map[my_j[q]] : 0;
             my_v[q] = mine < p1[q] ? (val ? val[mine] : 1.f) : 0.f;
             if (kDiag == 1) my_v[q] *= dropout_diag_factor(my_j[q], dd.n, dd.key, dd.thr, dd.scale);
         }
@@ -258,10 +268,11 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
         float self_c[kRows];
 #pragma unroll
         for (int q = 0; q < kRows; ++q) {
-            const bool live = self_coef != nullptr && r0 + q < n_rows;
+            const bool live = self_coef != nullptr && r0 + q < ((kMap && kDiag == 2) ? rm.n_self : n_rows);
+            const int64_t g_self = (kMap && kDiag == 1 && live) ? rm.map[r0 + q] : r0 + q;
             self_c[q] = live ? self_coef[r0 + q] : 0.f;
-            if (kDiag == 1 && live) self_c[q] *= dropout_diag_factor(r0 + q, dd.n, dd.key, dd.thr, dd.scale);
-            self_row[q] = (live && col_live) ? *(const float4*)(S + (r0 + q) * F + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (kDiag == 1 && live) self_c[q] *= dropout_diag_factor(g_self, dd.n, dd.key, dd.thr, dd.scale);
+            self_row[q] = (live && col_live) ? *(const float4*)(S + g_self * F + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int q = 0; q < kRows; ++q) {
@@ -269,6 +280,7 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
                 if (base != p0[q]) {                       // rows with more than kLanes entries: next chunk
                     const int mine = base + lane;
                     my_j[q] = mine < p1[q] ? idx[mine] : 0;
+                    if (kMap && kDiag == 1) my_j[q] = mine < p1[q] ? (int)rm.map[my_j[q]] : 0;
                     my_v[q] = mine < p1[q] ? (val ? val[mine] : 1.f) : 0.f;
                     if (kDiag == 1) my_v[q] *= dropout_diag_factor(my_j[q], dd.n, dd.key, dd.thr, dd.scale);
                 }
@@ -300,11 +312,12 @@ __global__ __launch_bounds__(kBlock) void k_spmm_v4(const int32_t* __restrict__ 
             o.x += self_c[q] * self_row[q].x + b.x; o.y += self_c[q] * self_row[q].y + b.y;
             o.z += self_c[q] * self_row[q].z + b.z; o.w += self_c[q] * self_row[q].w + b.w;
             if (act) o = elu_fast4(o);
+            const int64_t g_out = (kMap && kDiag == 2) ? rm.map[r0 + q] : r0 + q;
             if (kDiag == 2) {
-                const float d = dropout_diag_factor(r0 + q, dd.n, dd.key, dd.thr, dd.scale);
+                const float d = dropout_diag_factor(g_out, dd.n, dd.key, dd.thr, dd.scale);
                 o.x *= d; o.y *= d; o.z *= d; o.w *= d;
             }
-            *(float4*)(Y + (r0 + q) * F + c0) = o;
+            *(float4*)(Y + g_out * F + c0) = o;
         }
     }
 }
@@ -712,12 +725,16 @@ static int launch_spmm(const int32_t* ptr, const int32_t* idx, const float* val,
 
 // the float4 kernels with a diagonal dropout factor (where = 1: on the source rows, 2: on the output rows); F % 4 == 0, F <= 256, no hub rows
 static int launch_spmm_diag(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, const float* X, int F, const float* self_coef,
-                            const float* S, const float* bias, int act, int where, DiagDrop dd, float* Y, hipStream_t st) {
+                            const float* S, const float* bias, int act, int where, DiagDrop dd, float* Y, hipStream_t st,
+                            RowMap rm = RowMap{nullptr, 0}) {
     if (n_rows == 0 || F == 0) return PP_OK;
     const HeavyRows none{nullptr, nullptr};
 #define PP_SPMM_D4(L, FULL)                                                                                                                   \
     do {                                                                                                                                      \
-        if (where == 1) k_spmm_v4<L, 2, FULL, 1><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd);  \
+        if (rm.map != nullptr) {                                                                                                              \
+            if (where == 1) k_spmm_v4<L, 2, FULL, 1, true><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd, rm);  \
+            else k_spmm_v4<L, 2, FULL, 2, true><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd, rm);             \
+        } else if (where == 1) k_spmm_v4<L, 2, FULL, 1><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd);  \
         else k_spmm_v4<L, 2, FULL, 2><<<grid, kBlock, 0, st>>>(ptr, idx, val, n_rows, X, F, self_coef, S, bias, act, none, Y, dd);             \
     } while (0)
 #define PP_SPMM_D(L)                                                                  \
@@ -927,6 +944,23 @@ int pp_spmm_diag_drop_f32(const int32_t* ptr, const int32_t* idx, const float* v
     const DropSite d = drop_site(p, seed, tag, 0);
     return launch_spmm_diag(ptr, idx, val, n_rows, X, F, self_coef, self_coef ? X : nullptr, bias, act, where, DiagDrop{d.key, d.thr, d.scale, (int)n}, Y,
                             (hipStream_t)stream);
+}
+
+int pp_spmm_diag_drop_map_f32(const int32_t* ptr, const int32_t* idx, const float* val, int64_t n_rows, int64_t n_self, const float* X, int F,
+                              const float* self_coef, const float* bias, int act, int where, const int64_t* map, int64_t n, double p, int64_t seed,
+                              int64_t tag, float* Y, pp_stream_t stream) {
+    PP_REQUIRE(n_rows >= 0 && n_self >= 0 && n_self <= n_rows, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: need 0 <= n_self <= n_rows");
+    PP_REQUIRE(F >= 4 && F % 4 == 0 && F <= 256, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: F must be a multiple of 4 in [4, 256]");
+    PP_REQUIRE(((uintptr_t)X | (uintptr_t)Y | (uintptr_t)bias) % 16 == 0, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: 16-byte alignment");
+    PP_REQUIRE(act == 0 || act == 1, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: act must be 0 (none) or 1 (elu)");
+    PP_REQUIRE((where == 1 && n_self == n_rows) || (where == 2 && act == 0 && bias == nullptr), PP_ERR_ARG,
+               "pp_spmm_diag_drop_map_f32: where must be 1 (source rows; n_self = n_rows) or 2 (output rows; then without bias and activation)");
+    PP_REQUIRE(map != nullptr || n_rows == 0, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: map is required");
+    PP_REQUIRE(p >= 0.0 && p < 1.0, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: p must lie in [0, 1)");
+    PP_REQUIRE(n >= 1 && n < (int64_t)0x7fffffff, PP_ERR_ARG, "pp_spmm_diag_drop_map_f32: need 1 <= n < 2^31");
+    const DropSite d = drop_site(p, seed, tag, 0);
+    return launch_spmm_diag(ptr, idx, val, n_rows, X, F, self_coef, self_coef ? X : nullptr, bias, act, where, DiagDrop{d.key, d.thr, d.scale, (int)n}, Y,
+                            (hipStream_t)stream, RowMap{map, n_self});
 }
 
 // out_max[0] = max_r (ptr[r+1] - ptr[r]) of a CSR row-pointer array (device int64): does the plan have hub rows?

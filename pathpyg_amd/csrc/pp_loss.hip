@@ -22,6 +22,23 @@ struct MaskedSums {                      // the device result of pp_cross_entrop
     int64_t selected, out_of_range;
 };
 
+struct MaskedRaw {                       // the same sums BEFORE the rounding to fp32 (pp_cross_entropy_masked_sums_f32, 32 bytes): what a rank of a
+    double num, den;                     // partitioned run adds to its peers' sums — fp32 sums of different ranks could not be added without a
+    int64_t selected, out_of_range;      // second rounding
+};
+
+// the one place where sums become the result: pp_cross_entropy_masked_f32 (one process) and pp_masked_finish_f32 (sums of all ranks) share it
+__device__ __forceinline__ MaskedSums finish_sums(double a, double b, int64_t s, int64_t o) {
+    MaskedSums r;
+    r.num = (float)a;
+    r.den = (float)b;
+    r.mean = (float)(a / b);                               // 0 / 0 = NaN on an empty selection, as F.cross_entropy's mean
+    r.inv_den = s - o > 0 ? (float)(1.0 / b) : 0.f;          // ... whose gradient is all zero, not 0 * inf
+    r.selected = s;
+    r.out_of_range = o;
+    return r;
+}
+
 __device__ __forceinline__ bool row_selected(const uint8_t* __restrict__ mask, const int64_t* __restrict__ target, int64_t i, int64_t ignore_index,
                                              int use_ignore, int64_t& y) {
     if (mask && mask[i] == 0) return false;
@@ -114,7 +131,7 @@ __global__ __launch_bounds__(kBlock) void k_cross_entropy_masked(const float* __
 // out = the sums of the n_parts per-workgroup partials in a fixed order (thread j takes j, j + 256, ..; fixed-shape tree over the threads)
 __global__ __launch_bounds__(kBlock) void k_masked_finish(const double* __restrict__ part_num, const double* __restrict__ part_den,
                                                          const int64_t* __restrict__ part_sel, const int64_t* __restrict__ part_bad, int n_parts,
-                                                         MaskedSums* __restrict__ out) {
+                                                         MaskedSums* __restrict__ out, MaskedRaw* __restrict__ raw) {
     __shared__ double s_num[kWavesPerBlock], s_den[kWavesPerBlock];
     __shared__ int64_t s_sel[kWavesPerBlock], s_bad[kWavesPerBlock];
     double a = 0.0, b = 0.0;
@@ -146,15 +163,14 @@ __global__ __launch_bounds__(kBlock) void k_masked_finish(const double* __restri
             s += s_sel[wv];
             o += s_bad[wv];
         }
-        MaskedSums r;
-        r.num = (float)a;
-        r.den = (float)b;
-        r.mean = (float)(a / b);                               // 0 / 0 = NaN on an empty selection, as F.cross_entropy's mean
-        r.inv_den = s - o > 0 ? (float)(1.0 / b) : 0.f;          // ... whose gradient is all zero, not 0 * inf
-        r.selected = s;
-        r.out_of_range = o;
-        *out = r;
+        if (out) *out = finish_sums(a, b, s, o);
+        if (raw) *raw = MaskedRaw{a, b, s, o};
     }
+}
+
+// sums of all ranks (reduced by the caller) -> the result, with the arithmetic of k_masked_finish
+__global__ void k_masked_finish_reduced(const double* __restrict__ sums, const int64_t* __restrict__ counts, MaskedSums* __restrict__ out) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *out = finish_sums(sums[0], sums[1], counts[0], counts[1]);
 }
 
 // counts[y][argmax z] += 1 over the selected rows: one lane per row, a per-workgroup histogram in LDS (C * C words: 16 KB at C = 64), its
@@ -250,13 +266,13 @@ extern "C" {
 
 size_t pp_cross_entropy_masked_ws_bytes(void) { return 4 * pp::align_up((size_t)pp::kMaxGrid * sizeof(double)); }
 
-int pp_cross_entropy_masked_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
-                                int64_t ignore_index, int use_ignore, void* result, float* dlogits_raw, void* ws, size_t ws_bytes, pp_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
+static int masked_entry(const char* what, const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
+                        int64_t ignore_index, int use_ignore, pp::MaskedSums* result, pp::MaskedRaw* raw, float* dlogits_raw, void* ws, size_t ws_bytes,
+                        hipStream_t st) {
     static_assert(sizeof(pp::MaskedSums) == 32, "the result is 4 floats and 2 int64");
-    PP_REQUIRE(n >= 0 && C >= 1 && C <= 64, PP_ERR_ARG, "pp_cross_entropy_masked_f32: needs 1 <= C <= 64 (got %d)", C);
-    PP_REQUIRE(result != nullptr && (uintptr_t)result % 8 == 0, PP_ERR_ARG, "pp_cross_entropy_masked_f32: result must be 32 bytes, 8-byte aligned");
-    PP_REQUIRE(ws != nullptr && ws_bytes >= pp_cross_entropy_masked_ws_bytes(), PP_ERR_WORKSPACE, "pp_cross_entropy_masked_f32: workspace too small");
+    static_assert(sizeof(pp::MaskedRaw) == 32, "the raw sums are 2 doubles and 2 int64");
+    PP_REQUIRE(n >= 0 && C >= 1 && C <= 64, PP_ERR_ARG, "%s: needs 1 <= C <= 64 (got %d)", what, C);
+    PP_REQUIRE(ws != nullptr && ws_bytes >= pp_cross_entropy_masked_ws_bytes(), PP_ERR_WORKSPACE, "%s: workspace too small", what);
     pp::Arena arena(ws, ws_bytes);
     pp::MaskedParts p;
     p.num = arena.take<double>(pp::kMaxGrid);
@@ -274,7 +290,30 @@ int pp_cross_entropy_masked_f32(const float* logits, const int64_t* target, cons
         else rc = pp::launch_masked<64, false>(st, logits, target, mask, weight, n, C, ignore_index, use_ignore, p, dlogits_raw, &blocks);
         if (rc != PP_OK) return rc;
     }
-    pp::k_masked_finish<<<1, pp::kBlock, 0, st>>>(p.num, p.den, p.sel, p.bad, (int)blocks, (pp::MaskedSums*)result);
+    pp::k_masked_finish<<<1, pp::kBlock, 0, st>>>(p.num, p.den, p.sel, p.bad, (int)blocks, result, raw);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_cross_entropy_masked_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
+                                int64_t ignore_index, int use_ignore, void* result, float* dlogits_raw, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    PP_REQUIRE(result != nullptr && (uintptr_t)result % 8 == 0, PP_ERR_ARG, "pp_cross_entropy_masked_f32: result must be 32 bytes, 8-byte aligned");
+    return masked_entry("pp_cross_entropy_masked_f32", logits, target, mask, weight, n, C, ignore_index, use_ignore, (pp::MaskedSums*)result, nullptr,
+                        dlogits_raw, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int pp_cross_entropy_masked_sums_f32(const float* logits, const int64_t* target, const uint8_t* mask, const float* weight, int64_t n, int C,
+                                     int64_t ignore_index, int use_ignore, void* raw_sums, float* dlogits_raw, void* ws, size_t ws_bytes,
+                                     pp_stream_t stream) {
+    PP_REQUIRE(raw_sums != nullptr && (uintptr_t)raw_sums % 8 == 0, PP_ERR_ARG, "pp_cross_entropy_masked_sums_f32: raw_sums must be 32 bytes, 8-byte aligned");
+    return masked_entry("pp_cross_entropy_masked_sums_f32", logits, target, mask, weight, n, C, ignore_index, use_ignore, nullptr,
+                        (pp::MaskedRaw*)raw_sums, dlogits_raw, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int pp_masked_finish_f32(const double* sums, const int64_t* counts, void* result, pp_stream_t stream) {
+    PP_REQUIRE(sums != nullptr && counts != nullptr, PP_ERR_ARG, "pp_masked_finish_f32: sums [2] and counts [2] are required");
+    PP_REQUIRE(result != nullptr && (uintptr_t)result % 8 == 0, PP_ERR_ARG, "pp_masked_finish_f32: result must be 32 bytes, 8-byte aligned");
+    pp::k_masked_finish_reduced<<<1, 1, 0, (hipStream_t)stream>>>(sums, counts, (pp::MaskedSums*)result);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -795,7 +795,10 @@ def _bipartite_shard(ho_local: torch.Tensor, fo_global: torch.Tensor, n_ho_own: 
 def shard_dbgnn_bundle(data, comm: Comm, ops=None, fo_cuts: list[int] | None = None, ho_cuts: list[int] | None = None):
     """Partition a REPLICATED ``MultiOrderModel.to_dbgnn_data`` bundle (reference multi_order_model.py:511-554) for this rank: the edges
     into its first-order / higher-order destination ranges, the bipartite pairs of its higher-order rows, its feature rows (owned +
-    halo, taken from the replicated inputs: no exchange for the first layer) and labels.  ``fo_cuts`` / ``ho_cuts``: row cuts
+    halo, taken from the replicated inputs: no exchange for the first layer), labels and node splits (``train_mask`` / ``val_mask`` /
+    ``test_mask`` where the bundle has them, ``utils.random_node_split``: ``shard.masks``).  Features that are still the identity by
+    construction (``Data.is_identity``: the default of ``to_dbgnn_data``) stay implicit: the shard stores ``None`` and the graph shard's row
+    map instead of ``(n_own + n_halo) x n`` floats, and nothing is resolved.  ``fo_cuts`` / ``ho_cuts``: row cuts
     (default: equal node counts; for a De Bruijn layer cut the higher-order ids at first-order node boundaries to get the
     one-peer-per-row exchange)."""
     from .nn.sharded import DbgnnShard
@@ -828,10 +831,42 @@ def shard_dbgnn_bundle(data, comm: Comm, ops=None, fo_cuts: list[int] | None = N
     bip, cap = _bipartite_shard(bi_ho, bi_fo, ho.n_own, fo_cuts, comm, ops, src_sorted=False)
     ops.check_plan_status(pending)
     indeg = torch.bincount(bi[1], minlength=n_fo)[fo_cuts[rank]: fo_cuts[rank + 1]].to(torch.float32)
-    x = data.x.index_select(0, fo.local_rows()) if world > 1 else data.x
-    x_h = data.x_h.index_select(0, ho.local_rows()) if world > 1 else data.x_h
+    probe = getattr(data, "is_identity", None)
+
+    def features(name, gs, nodes):
+        if probe is not None and probe(name) and int(data.peek(name).shape[0]) == nodes:
+            return None                  # one-hot by construction: kept implicit (see _keep_implicit)
+        full = getattr(data, name)
+        return (full.index_select(0, gs.local_rows()) if world > 1 else full).contiguous()
+
+    x, x_h = features("x", fo, n_fo), features("x_h", ho, n_ho)
     y = None if data.y is None else data.y[fo_cuts[rank]: fo_cuts[rank + 1]]
-    return DbgnnShard(fo=fo, ho=ho, bip=bip, cap=cap, indeg=indeg, x=x.contiguous(), x_h=x_h.contiguous(), y=y, n_fo=n_fo, n_ho=n_ho)
+    masks = {}
+    for name in ("train_mask", "val_mask", "test_mask"):
+        full = getattr(data, name, None)
+        if isinstance(full, torch.Tensor) and full.dim() == 1 and full.size(0) == n_fo:
+            masks[name] = full[fo_cuts[rank]: fo_cuts[rank + 1]].to(torch.bool).contiguous()
+    return _keep_implicit(DbgnnShard(fo=fo, ho=ho, bip=bip, cap=cap, indeg=indeg, x=x, x_h=x_h, y=y, n_fo=n_fo, n_ho=n_ho, masks=masks))
+
+
+def _keep_implicit(shard):
+    """Graphs of a :class:`~pathpyg_amd.nn.sharded.DbgnnShard` without feature rows (``x`` / ``x_h`` = None: the default one-hot features)
+    get their row map ``local slot -> global id`` — :meth:`GraphShard.local_rows`, taken HERE once because on shards of the node-by-node
+    builder it is an exchange (``halo_fetch``): a collective that every rank enters alike, since all ranks were given the same ``None``."""
+    if shard.x is None:
+        shard.fo.rows = shard.fo.local_rows().contiguous()
+    if shard.x_h is None:
+        shard.ho.rows = shard.ho.local_rows().contiguous()
+    return shard
+
+
+def _own_masks(masks, lo: int, hi: int, device) -> dict:
+    """Node splits of the owned first-order nodes ``lo .. hi`` from replicated bool ``[n]`` tensors or row loaders (served as ``y`` is)."""
+    return {name: _rows_of(source, None, lo, hi, device).to(torch.bool).contiguous() for name, source in (masks or {}).items()}
+
+
+def _contiguous(t):
+    return None if t is None else t.contiguous()
 
 
 FUSED_BUILDER = True   # build_dbgnn_shard at world size 1: the node-by-node order-2 builder (pp_debruijn2_*, one read-back, no event graph) where it
@@ -947,7 +982,7 @@ def _route(keys_owner: torch.Tensor, world: int, ops):
     return ptr, order.long()
 
 
-def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "edge_weight", defer_status: bool = False):
+def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "edge_weight", defer_status: bool = False, masks=None):
     """The north-star split, straight from a time-sorted event stream replicated on every rank (what it replaces on one process:
     ``MultiOrderModel.from_temporal_graph(g, delta, max_order=2)`` + ``to_dbgnn_data`` + the plans of ``DBGNN.forward``; reference
     multi_order_model.py:124-192, 511-554, algorithms/temporal.py:17-54, lift_order.py:109-152).
@@ -969,7 +1004,11 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
     5. graph shards (rectangular GCN plans with one d^-1/2 halo exchange each), the bipartite "last" plan, local feature rows.
 
     ``x`` [N, F] / ``x_h`` [U_2, F] / ``y`` [N]: replicated tensors, or ROW LOADERS ``f(rows int64) -> tensor`` (``x_h`` may also be a
-    callable of the node count, the round-2 form, when it takes an ``int``) — a rank only ever reads its owned + halo rows.
+    callable of the node count, the round-2 form, when it takes an ``int``) — a rank only ever reads its owned + halo rows.  ``x=None`` /
+    ``x_h=None``: the default one-hot features of that graph (``torch.eye``), kept implicit — no feature row is loaded or exchanged for it, the
+    shard keeps the graph shard's row map instead (``GraphShard.rows``) and the model's first layer reads ``W^T`` through it.
+    ``masks``: dict name -> replicated bool ``[N]`` tensor or row loader (node splits, e.g. ``train`` / ``test``): ``shard.masks`` holds the
+    owned nodes' entries, for ``ShardedDBGNN.loss(shard, mask=name)`` / ``evaluate``.
     ``defer_status=True`` (world size 1, generic kernels): the higher-order plan's report (bad-index status, hub-row tables) is left to
     ``DbgnnShard.resolve()`` — which :class:`~pathpyg_amd.nn.sharded.ShardedDBGNN` calls after it has queued the first-order layers, so the
     read-back costs no idle GPU time; a caller that uses ``shard.ho.plan`` directly must call ``resolve()`` first.  Default: resolved here.
@@ -977,10 +1016,10 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
     ops = _ops_default(ops)
     if comm.world > 1:
         if FUSED_BUILDER and getattr(ops, "debruijn2_part_count", None) is not None:
-            shard = _build_partitioned_by_node(g, delta, x, x_h, y, comm, ops, weight)
+            shard = _build_partitioned_by_node(g, delta, x, x_h, y, comm, ops, weight, masks)
             if shard is not None:
-                return shard
-        return _build_partitioned(g, delta, x, x_h, y, comm, ops, weight)
+                return _keep_implicit(shard)
+        return _keep_implicit(_build_partitioned(g, delta, x, x_h, y, comm, ops, weight, masks))
     from .nn.sharded import DbgnnShard
     data = g.data
     ei = _dispatch.plain(data.edge_index)
@@ -998,11 +1037,13 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
                 return GraphShard(lo=0, hi=nodes, n_own=nodes, n_halo=0, n_src=nodes, num_nodes=nodes, cuts=[0, nodes], plan=plan, send_counts=[0],
                                   recv_counts=[0])
             xh_loc = x_h(n_ho) if (callable(x_h) and _takes_count(x_h)) else _rows_of(x_h, None, 0, n_ho, dev)
-            return DbgnnShard(fo=whole(built.fo, n), ho=whole(built.ho, n_ho), bip=built.bip, cap=n, indeg=built.bip.self_coef,
-                              x=_rows_of(x, None, 0, n, dev).contiguous(), x_h=xh_loc.contiguous(), y=_rows_of(y, None, 0, n, dev), n_fo=n, n_ho=n_ho,
+            return _keep_implicit(DbgnnShard(
+                              fo=whole(built.fo, n), ho=whole(built.ho, n_ho), bip=built.bip, cap=n, indeg=built.bip.self_coef,
+                              x=_contiguous(_rows_of(x, None, 0, n, dev)), x_h=_contiguous(xh_loc), y=_rows_of(y, None, 0, n, dev), n_fo=n, n_ho=n_ho,
+                              masks=_own_masks(masks, 0, n, dev),
                               sizes={"m": m, "N": n, "E2": built.sizes["E2"], "E2_local": built.sizes["E2"], "U2": n_ho, "A1": built.sizes["A1"],
                                      "A2": built.sizes["A2"], "A2_local": built.sizes["A2"], "fo_cuts": [0, n], "ho_cuts": [0, n_ho], "fo_halo": 0,
-                                     "ho_halo": 0, "builder": "fused"})
+                                     "ho_halo": 0, "builder": "fused"}))
     w = _hip.UNIT if unit_weights else data[weight]                         # (unit weights: merged weight = run length, no ones vector, no gather)
     # layer 1 and the lift of the same stream are independent: their count phases are queued together, their sizes cost ONE read-back
     (fo, fo_w, inv1), local = ops.coalesce_and_lift((ei, w, n, "sum", None, True), (ei, data.time.contiguous(), n, delta, m, 0))
@@ -1026,10 +1067,11 @@ def build_dbgnn_shard(g, delta, x, x_h, y, comm: Comm, ops=None, weight: str = "
     xh_loc = x_h(n_ho) if (callable(x_h) and _takes_count(x_h)) else _rows_of(x_h, None, 0, n_ho, dev)
     a2 = int(ho_ei.size(1))
     # defer_status: the higher-order plan's report is read by DbgnnShard.resolve() — ShardedDBGNN queues the first-order layers in front of it
-    shard = DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=n, indeg=indeg, x=x_loc.contiguous(), x_h=xh_loc.contiguous(), y=_rows_of(y, None, 0, n, dev),
-                      n_fo=n, n_ho=n_ho, pending=(ops, pending_ho),
+    shard = DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=n, indeg=indeg, x=_contiguous(x_loc), x_h=_contiguous(xh_loc), y=_rows_of(y, None, 0, n, dev),
+                      n_fo=n, n_ho=n_ho, pending=(ops, pending_ho), masks=_own_masks(masks, 0, n, dev),
                       sizes={"m": m, "N": n, "E2": e2, "E2_local": e2, "U2": n_ho, "A1": n_ho, "A2": a2, "A2_local": a2, "fo_cuts": fo_cuts,
                              "ho_cuts": ho_cuts, "fo_halo": 0, "ho_halo": 0})
+    _keep_implicit(shard)
     return shard if defer_status else shard.resolve()
 
 
@@ -1038,7 +1080,7 @@ def global_sizes(shard, comm: Comm) -> dict:
     :func:`build_dbgnn_shard` so that a step pays no all-reduce for a number only reports need)."""
     sizes = dict(shard.sizes)
     if "A2" not in sizes:
-        total = torch.tensor([sizes["A2_local"]], dtype=torch.float64, device=shard.x.device)
+        total = torch.tensor([sizes["A2_local"]], dtype=torch.float64, device=shard.device)
         comm.all_reduce_(total)
         sizes["A2"] = int(total.item())
     return sizes
@@ -1182,7 +1224,7 @@ def _own_rows_buffer(source, lo: int, hi: int, row_of: torch.Tensor, n_halo: int
     return buf
 
 
-def _build_partitioned_by_node(g, delta, x, x_h, y, comm: Comm, ops, weight: str):
+def _build_partitioned_by_node(g, delta, x, x_h, y, comm: Comm, ops, weight: str, masks=None):
     """World size > 1, round 4: NODE-RANGE partition on the node-by-node order-2 builder.  Rank r owns the first-order nodes of its range, is
     handed the events that touch them (:func:`distribute_stream_by_node`, once per stream) and builds — with one read-back and without any
     exchange of pairs, node ids or counts — the order-2 rows (b, .) of its nodes b: their in-edges come from in-events x out-events of b, all
@@ -1220,8 +1262,10 @@ def _build_partitioned_by_node(g, delta, x, x_h, y, comm: Comm, ops, weight: str
     # input features of the halo rows travel under the rest of the build; the halo rows' degrees are needed by the fill pass
     if callable(x_h) and _takes_count(x_h):
         x_h = x_h(n_ho)
-    xh_buf = _own_rows_buffer(x_h, lo_h, hi_h, c.row_of, n_halo, dev)          # (owned rows in the shard's local order = send order: no pack below)
-    xh_pending = comm.exchange_rows_async(xh_buf[: c.n_send], c.send_counts, c.recv_counts, out=xh_buf[n_own: n_own + n_halo])
+    xh_buf = xh_pending = None                                               # (x_h = None: implicit one-hot features, no rows and no exchange)
+    if x_h is not None:
+        xh_buf = _own_rows_buffer(x_h, lo_h, hi_h, c.row_of, n_halo, dev)      # (owned rows in the shard's local order = send order: no pack below)
+        xh_pending = comm.exchange_rows_async(xh_buf[: c.n_send], c.send_counts, c.recv_counts, out=xh_buf[n_own: n_own + n_halo])
     comm.exchange_rows(c.ho_deg[: c.n_send], c.send_counts, c.recv_counts, out=c.ho_deg[n_own: n_own + n_halo])
     comm.mark("build: 2 halo exchanges (degrees; feature rows asynchronously)")
     # first-order degrees of ALL nodes (the count pass filled my slice): one all-gather of N floats
@@ -1253,16 +1297,17 @@ def _build_partitioned_by_node(g, delta, x, x_h, y, comm: Comm, ops, weight: str
         bip, cap = _bipartite_shard(torch.arange(n_own, dtype=torch.int64, device=dev), c.succ.to(torch.int64), n_own, fo_cuts, comm, ops, src_sorted=True)
     ops.check_plan_status(pending)
     comm.mark("build: bipartite plan")
-    x_loc = _shard_rows(x, fo_shard, comm)
-    xh_pending.wait()
+    x_loc = None if x is None else _shard_rows(x, fo_shard, comm)
+    if xh_pending is not None:
+        xh_pending.wait()
     comm.mark("build: feature rows (owned + halo)")
-    return DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=cap, indeg=indeg, x=x_loc.contiguous(), x_h=xh_buf[: n_own + n_halo],
-                      y=_rows_of(y, None, lo_n, hi_n, dev), n_fo=n, n_ho=n_ho,
+    return DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=cap, indeg=indeg, x=_contiguous(x_loc), x_h=None if xh_buf is None else xh_buf[: n_own + n_halo],
+                      y=_rows_of(y, None, lo_n, hi_n, dev), n_fo=n, n_ho=n_ho, masks=_own_masks(masks, lo_n, hi_n, dev),
                       sizes={"m": ns.m, "N": n, "E2": e2, "E2_local": c.e2, "U2": n_ho, "A1": n_ho, "A2_local": c.a2, "fo_cuts": fo_cuts,
                              "ho_cuts": ho_cuts, "fo_halo": fo_shard.n_halo, "ho_halo": n_halo, "events_local": int(ns.ei.size(1)), "builder": "fused"})
 
 
-def _build_partitioned(g, delta, x, x_h, y, comm: Comm, ops, weight: str):
+def _build_partitioned(g, delta, x, x_h, y, comm: Comm, ops, weight: str, masks=None):
     """World size > 1 branch of :func:`build_dbgnn_shard` (see there for the scheme)."""
     from .nn.sharded import DbgnnShard
     rank, world = comm.rank, comm.world
@@ -1356,13 +1401,13 @@ def _build_partitioned(g, delta, x, x_h, y, comm: Comm, ops, weight: str):
     fptr = fo_shard.plan.fwd_ptr
     indeg = (fptr[1:] - fptr[:-1]).to(torch.float32)                            # order-2 nodes (., b) per owned first-order node b
     comm.mark("build: bipartite plan + status read-back")
-    x_loc = _shard_rows(x, fo_shard, comm)
+    x_loc = None if x is None else _shard_rows(x, fo_shard, comm)
     if callable(x_h) and _takes_count(x_h):
         x_h = x_h(n_ho)
-    xh_loc = _shard_rows(x_h, ho, comm)
+    xh_loc = None if x_h is None else _shard_rows(x_h, ho, comm)
     comm.mark("build: feature rows (owned + halo)")
-    return DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=cap, indeg=indeg, x=x_loc.contiguous(), x_h=xh_loc.contiguous(),
-                      y=_rows_of(y, None, lo_n, hi_n, dev), n_fo=n, n_ho=n_ho,
+    return DbgnnShard(fo=fo_shard, ho=ho, bip=bip, cap=cap, indeg=indeg, x=_contiguous(x_loc), x_h=_contiguous(xh_loc),
+                      y=_rows_of(y, None, lo_n, hi_n, dev), n_fo=n, n_ho=n_ho, masks=_own_masks(masks, lo_n, hi_n, dev),
                       sizes={"m": m, "N": n, "E2": e2, "E2_local": e2_local, "U2": n_ho, "A1": n_ho, "A2_local": int(ho_ei.size(1)),
                              "fo_cuts": fo_cuts, "ho_cuts": ho_cuts, "ev_cuts": plan["ev_cuts"], "fo_halo": fo_shard.n_halo, "ho_halo": ho.n_halo,
                              "lift_events_local": int(ss.ei_lift.size(1)), "layer1_events_local": m_l1})

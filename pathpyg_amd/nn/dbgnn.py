@@ -571,6 +571,12 @@ def evaluate(logits: torch.Tensor, target: torch.Tensor, *, mask=None, ignore_in
         confusion = torch.from_numpy(conf).to(logits.device)
     if bad:
         raise IndexError(f"evaluate: {bad} selected target(s) outside [0, {c})")
+    return scores_from_confusion(conf, confusion)
+
+
+def scores_from_confusion(conf: np.ndarray, confusion: torch.Tensor) -> dict:
+    """The dict of :func:`evaluate` from a confusion matrix on the host (``conf`` [C, C], row = true class) — shared with the partitioned
+    model, whose matrix is the sum of its ranks' (``ShardedDBGNN.evaluate``); ``confusion`` is the tensor handed back under that key."""
     conf = conf.astype(np.float64)
     support, predicted, hit = conf.sum(1), conf.sum(0), np.diag(conf)
     total = support.sum()

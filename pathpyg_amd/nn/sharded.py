@@ -266,6 +266,60 @@ class HipOps:
         from .dbgnn import cross_entropy
         return cross_entropy(logits, target)
 
+    # ---- the loss and the scores of a node split, one rank's part (the collectives are ShardedDBGNN's: _ShardedMaskedLoss, evaluate)
+    @staticmethod
+    def masked_sums(logits, target, mask, weight, ignore_index, want_grad: bool):
+        """``(sums float64 [2] = (sum w[y] nll, sum w[y]), counts int64 [2] = (selected, out of range), raw gradient of the sum or None)`` over
+        this rank's selected rows (pp_cross_entropy_masked_sums_f32; an empty share gives zeros)."""
+        raw, grad = _hip.cross_entropy_masked_sums(logits, target, mask, weight, ignore_index, want_grad=want_grad)
+        return raw.sums, raw.counts, grad
+
+    @staticmethod
+    def masked_finish(sums, counts):
+        """fp32 ``[4] = (num, den, mean, 1 / den or 0)`` of the (reduced) sums, rounded once (pp_masked_finish_f32)."""
+        return _hip.masked_finish(sums, counts).values
+
+    @staticmethod
+    def confusion_counts(logits, target, mask, ignore_index):
+        """int64 ``[C * C + 1]``: this rank's confusion matrix and its count of selected targets outside [0, C) (pp_confusion_f32)."""
+        return _hip.confusion(logits, target, mask, ignore_index, with_status=True)
+
+    # ---- first GCN layer on the default one-hot features (x = None): ELU(A_hat diag(d) W^T + b) on the owned rows, W^T [n, F] replicated,
+    # local slot -> global id through the shard's row map; d = the factors of dropout_mask_diagonal (all ones without dropout)
+    ONE_HOT_FUSED = True               # False: always the composition of the pre-existing kernels (A/B measurements)
+
+    @staticmethod
+    def one_hot_fused_ok(plan, width: int) -> bool:
+        return (HipOps.ONE_HOT_FUSED and plan.self_coef is not None and _hip.spmm_diag_drop_supported(width, plan.fwd_heavy)
+                and _hip.spmm_diag_drop_supported(width, plan.bwd_heavy))
+
+    @staticmethod
+    def one_hot_forward(plan, wt: torch.Tensor, bias, rows: torch.Tensor, n: int, site, out: torch.Tensor) -> None:
+        """``out[:] = ELU(sum_p val[p] d[rows[idx[p]]] wt[rows[idx[p]]] + self_coef[r] d[rows[r]] wt[rows[r]] + b)``; ``site = (p, seed, tag)``
+        or None.  The row-mapped float4 kernel (pp_spmm_diag_drop_map_f32) where the width and the plan allow it; plans with hub rows and other
+        widths gather ``wt[rows]``, scale it and run the CSR kernel."""
+        p, seed, tag = site if site is not None else (0.0, 0, 0)
+        if HipOps.one_hot_fused_ok(plan, wt.size(1)):
+            _hip.spmm_diag_drop_map(plan.fwd_ptr, plan.fwd_idx, plan.fwd_val, plan.n_dst, wt, plan.self_coef, bias, True, 1, rows, n, p, seed, tag, out=out)
+            return
+        t = wt.index_select(0, rows)
+        if site is not None:
+            t.mul_(dropout_mask_diagonal(rows, n, p, seed, tag).unsqueeze(1))
+        out.copy_(_hip.spmm(plan.fwd_ptr, plan.fwd_idx, plan.fwd_val, plan.n_dst, t, plan.self_coef, t, bias, True, heavy=plan.fwd_heavy))
+
+    @staticmethod
+    def one_hot_backward(plan, dpre: torch.Tensor, rows: torch.Tensor, n: int, site) -> torch.Tensor:
+        """This rank's partial ``dW^T [n, F] = diag(d) (A^T dpre + diag(self) dpre)`` scattered to the global ids ``rows`` (zero elsewhere)."""
+        p, seed, tag = site if site is not None else (0.0, 0, 0)
+        if HipOps.one_hot_fused_ok(plan, dpre.size(1)):
+            return _hip.spmm_diag_drop_map(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, plan.n_src, dpre, plan.self_coef, None, False, 2, rows, n, p, seed,
+                                           tag, n_self=plan.n_dst)
+        g = _hip.spmm(plan.bwd_ptr, plan.bwd_idx, plan.bwd_val, plan.n_src, dpre, heavy=plan.bwd_heavy)
+        g[: plan.n_dst].addcmul_(dpre, plan.self_coef.unsqueeze(1))
+        if site is not None:
+            g.mul_(dropout_mask_diagonal(rows, n, p, seed, tag).unsqueeze(1))
+        return torch.zeros((n, dpre.size(1)), dtype=torch.float32, device=dpre.device).index_add_(0, rows, g)
+
 
 class GraphShard:
     """One rank's share of a graph under a destination-row partition (see the module docstring).
@@ -275,10 +329,12 @@ class GraphShard:
     ``send_idx`` / ``send_counts``: owned rows each peer asked for; ``recv_counts``: halo rows coming from each peer;
     ``back_ptr`` / ``back_idx``: CSR over the owned rows into the ``[n_send]`` buffer of returned gradient rows; ``send_unique``: every
     owned row is sent to at most one peer (De Bruijn layers cut at first-order node boundaries): returned rows are added in place;
-    ``send_slot`` (``send_unique`` shards): int32 ``[n_own]``, the position of an owned row in the send list or -1 — the inverse of ``send_idx``."""
+    ``send_slot`` (``send_unique`` shards): int32 ``[n_own]``, the position of an owned row in the send list or -1 — the inverse of ``send_idx``;
+    ``rows`` (graphs whose input features are the implicit one-hot default): int64 ``[n_src]``, local slot -> global id — :meth:`local_rows`
+    taken once when the shard is built (it can be a collective), all the first layer needs instead of feature rows."""
 
     __slots__ = ("lo", "hi", "n_own", "n_halo", "n_src", "num_nodes", "cuts", "plan", "halo_ids", "send_idx", "send_counts", "recv_counts",
-                 "back_ptr", "back_idx", "send_unique", "send_slot", "halo_fetch", "dense", "send_prefix", "own_ids")
+                 "back_ptr", "back_idx", "send_unique", "send_slot", "halo_fetch", "dense", "send_prefix", "own_ids", "rows")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -406,7 +462,10 @@ def dropout_mask_diagonal(rows: torch.Tensor, n: int, p: float, seed: int, tag: 
 class _ShardedGcnStack(torch.autograd.Function):
     """A stack of GCN layers ``h_{l+1} = ELU(A_hat h_l W_l^T + b_l)`` on this rank's destination rows.
 
-    Input ``x_full`` = ``[n_own + n_halo, F]`` features of the local source space (no gradient).  Output = the last layer's
+    Input ``x_full`` = ``[n_own + n_halo, F]`` features of the local source space (no gradient) — or None: the default one-hot features,
+    kept implicit.  The first parameter is then ``W_0^T [n, F]`` (replicated; the caller transposes, autograd transposes its gradient back) and
+    layer 0 is ``ELU(A_hat diag(d) W_0^T + b_0)`` read through ``shard.rows`` (``HipOps.one_hot_forward``); backward, the rank's partial
+    ``dW_0^T`` is zero outside its own slots' ids and the ranks' partials meet in the gradient all-reduce.  Output = the last layer's
     activation on the owned rows.  Contract as :class:`pathpyg_amd.nn.dbgnn._GcnLayer`: the consumer hands back the gradient
     w.r.t. the last layer's PRE-activation and computes that layer's bias gradient itself."""
 
@@ -420,20 +479,31 @@ class _ShardedGcnStack(torch.autograd.Function):
         plan, n_own = shard.plan, shard.n_own
         inputs, saved = [], []
         h = x_full
+        implicit = x_full is None
+        device = plan.fwd_ptr.device if implicit else x_full.device
         own_rows = getattr(shard, "own_ids", None)          # shards numbered in send order: masks by explicit global row ids, one extra pass
         if drop is not None:
             p_drop, seed, tag, out_tag = drop
-            h = ops.dropout(x_full, p_drop, seed, tag, 0, shard.local_rows() if (shard.n_halo or shard.lo or own_rows is not None) else None)
+            if not implicit:
+                h = ops.dropout(x_full, p_drop, seed, tag, 0, shard.local_rows() if (shard.n_halo or shard.lo or own_rows is not None) else None)
         for layer in range(n_layers):
             weight, bias = params[2 * layer], params[2 * layer + 1]
             last = layer == n_layers - 1
-            buf = torch.empty((n_own if last else shard.n_src, weight.size(0)), dtype=torch.float32, device=x_full.device)
+            width = weight.size(1) if (implicit and layer == 0) else weight.size(0)
+            buf = torch.empty((n_own if last else shard.n_src, width), dtype=torch.float32, device=device)
             inputs.append(h)
             # the next layer's input dropout is applied by the owner before the exchange — in the layer kernel's epilogue where the shape allows
             site_out = None
             if drop is not None and (not last or out_tag is not None):      # (the last layer's output: the dropout in front of the bipartite layer)
                 site_out = (p_drop, seed, out_tag if last else tag + layer + 1, shard.lo)
-            saved.append(ops.layer_forward(plan, h, weight, bias, layer == 0, buf[:n_own], site_out if own_rows is None else None))
+            if implicit and layer == 0:
+                # the input dropout of an identity is a factor per source row, inside the aggregation; the output's dropout is one pass behind it
+                ops.one_hot_forward(plan, weight, bias, shard.rows, shard.num_nodes, None if drop is None else (p_drop, seed, tag), buf[:n_own])
+                saved.append(None)
+                if site_out is not None and own_rows is None:
+                    ops.dropout(buf[:n_own], site_out[0], site_out[1], site_out[2], site_out[3], None, buf[:n_own])
+            else:
+                saved.append(ops.layer_forward(plan, h, weight, bias, layer == 0, buf[:n_own], site_out if own_rows is None else None))
             if site_out is not None and own_rows is not None:
                 ops.dropout(buf[:n_own], site_out[0], site_out[1], site_out[2], 0, own_rows, buf[:n_own])
             if not last:
@@ -455,7 +525,11 @@ class _ShardedGcnStack(torch.autograd.Function):
             weight = params[2 * layer]
             x_in = ctx.inputs[layer]
             if layer == 0:
-                grads[0] = ops.layer_backward(plan, d, x_in, weight, ctx.saved[0], False, None)[2]
+                if x_in is None:
+                    site = None if ctx.drop is None else ctx.drop[:3]
+                    grads[0] = ops.one_hot_backward(plan, d, shard.rows, shard.num_nodes, site)
+                else:
+                    grads[0] = ops.layer_backward(plan, d, x_in, weight, ctx.saved[0], False, None)[2]
                 break
             if (layer == 1 and FUSE_FIRST_DW and comm.world == 1 and ctx.drop is None and ctx.saved[0] is not None
                     and getattr(ops, "backward_below_ok", lambda p_, w_, a_: False)(plan, weight, ctx.saved[0])):
@@ -680,13 +754,23 @@ class _ShardedTrunk(torch.autograd.Function):
 
 class DbgnnShard:
     """Everything one rank needs for DBGNN steps on its partition: the two graph shards, the bipartite plan, the local input features
-    (owned + halo rows) and the labels of the owned first-order nodes."""
+    (owned + halo rows), the labels of the owned first-order nodes and their node splits.
 
-    __slots__ = ("fo", "ho", "bip", "cap", "indeg", "x", "x_h", "y", "n_fo", "n_ho", "sizes", "pending")
+    ``x`` / ``x_h`` = None: the default one-hot features of that graph, kept implicit — no feature row is stored; the graph shard's ``rows``
+    (local slot -> global id) is what the first layer reads ``W^T`` through.  ``masks``: name -> bool ``[n_own]`` on the shard's device, the
+    owned first-order nodes in the shard's row order, as ``y`` (``train_mask`` / ``val_mask`` / ``test_mask`` of a bundle; ``loss(mask=...)``)."""
+
+    __slots__ = ("fo", "ho", "bip", "cap", "indeg", "x", "x_h", "y", "n_fo", "n_ho", "sizes", "pending", "masks")
 
     def __init__(self, **kw):
         for k in self.__slots__:
             setattr(self, k, kw.get(k))
+        if self.masks is None:
+            self.masks = {}
+
+    @property
+    def device(self) -> torch.device:
+        return self.fo.plan.fwd_ptr.device
 
     def resolve(self) -> "DbgnnShard":
         """Read the report of the plans whose check was deferred (``pending = (ops, entries)``: bad-index status, hub rows of the
@@ -704,7 +788,9 @@ class ShardedDBGNN(torch.nn.Module):
 
     ``forward(shard)`` returns the logits of the first-order nodes this rank owns; ``loss(shard)`` the rank's share of the
     mean cross-entropy over ALL first-order nodes, so that summing the per-rank weight gradients
-    (``all_reduce_gradients(model, average=False)``) reproduces the single-process gradient.  Shards come from
+    (``all_reduce_gradients(model, average=False)``) reproduces the single-process gradient; ``loss(shard, mask=..., weight=...,
+    ignore_index=..., reduction=...)`` and ``evaluate(shard, mask=...)`` are the loss and the scores of a node split over the rows of all
+    ranks (one small all-reduce each).  Shards whose ``x`` / ``x_h`` is None run on the default one-hot features.  Shards come from
     :func:`pathpyg_amd.distributed.shard_dbgnn_bundle` (a replicated ``to_dbgnn_data`` bundle) or
     :func:`pathpyg_amd.distributed.build_dbgnn_shard` (straight from the event stream: sharded lift + aggregation)."""
 
@@ -726,13 +812,20 @@ class ShardedDBGNN(torch.nn.Module):
         dropping = m.p_dropout > 0 and m.training
         seed = 0
         if dropping:            # one seed per forward pass, the same on every rank (the masks are functions of the global row id)
-            pick = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).to(shard.x.device)
+            pick = torch.randint(0, 2 ** 31 - 1, (1,), dtype=torch.int64).to(shard.device)
             seed = int(comm.all_reduce_(pick, torch.distributed.ReduceOp.MAX).item()) if comm.world > 1 else int(pick.item())
+        self.last_seed = seed if dropping else None          # (the masks of this pass are a function of it: nn.dbgnn.DBGNN drops alike for the same seed)
 
         def stack(layers, graph_shard, x_full, tag, out_tag):
             params = []
             for layer in layers:
                 params += [layer.lin.weight, layer.bias]
+            if x_full is None:
+                # the default one-hot features: I W^T = W^T, the stack's first layer reads the rows of W^T through the shard's row map
+                if graph_shard.rows is None or params[0].size(1) != graph_shard.num_nodes:
+                    raise ValueError(f"ShardedDBGNN: implicit one-hot features need a first layer with {graph_shard.num_nodes} input features "
+                                     f"(got {params[0].size(1)}) and a shard built for them")
+                params[0] = params[0].t().contiguous()
             drop = (m.p_dropout, seed, tag, out_tag) if dropping else None
             return _ShardedGcnStack.apply(graph_shard, comm, ops, drop, x_full, *params), layers[-1].bias
 
@@ -740,7 +833,8 @@ class ShardedDBGNN(torch.nn.Module):
         head = getattr(ops, "head", None)       # (the CPU stand-ins of the distributed tests have none: they run the chain below)
         if comm.world > 1:
             shard.resolve()
-        if comm.world > 1 and not dropping and len(m.first_order_layers) == len(m.higher_order_layers) and self.overlap:
+        implicit = shard.x is None or shard.x_h is None          # (such stacks run the serial schedule below: _ShardedTrunk wants feature rows)
+        if comm.world > 1 and not dropping and not implicit and len(m.first_order_layers) == len(m.higher_order_layers) and self.overlap:
             # one schedule for both stacks + the bipartite sum: every exchange runs beside kernels of the other stack (_ShardedTrunk)
             params = []
             for layers in (m.first_order_layers, m.higher_order_layers):
@@ -772,9 +866,84 @@ class ShardedDBGNN(torch.nn.Module):
         x = ops.bip_combine(ops.dense_nobias(agg, bl.lin1.weight), ops.dense(x, bl.lin2, True, bias_fo), shard.indeg, bl.lin1.bias)
         return ops.dense(x, m.lin)
 
-    def loss(self, shard: DbgnnShard) -> torch.Tensor:
+    def loss(self, shard: DbgnnShard, *, mask=None, weight=None, ignore_index=None, reduction: str = "mean") -> torch.Tensor:
+        """This rank's share of the loss.  Without keywords: the mean cross-entropy over ALL first-order nodes.  With ``mask`` (a key of
+        ``shard.masks`` or a bool ``[n_own]`` tensor), ``weight`` (fp32 [C], replicated), ``ignore_index`` or ``reduction`` ("mean" / "sum"):
+        the share of ``F.cross_entropy(out[mask], y[mask], weight=, ignore_index=, reduction=)`` taken over the rows of ALL ranks, with the
+        semantics of :func:`pathpyg_amd.nn.cross_entropy` (exact zero gradient rows where unselected, no host read-back per step, NaN mean and
+        zero gradients on an empty global selection, IndexError on a selected target outside [0, C)).  The shares sum to the single-process
+        loss and ``all_reduce_gradients(net, average=False)`` of the ranks' gradients gives the single-process gradients.  One small
+        all-reduce per call carries the ranks' float64 sums (numerator, denominator) and the two counters, so the mean's denominator is
+        global and a bad target raises on EVERY rank (a rank raising alone would leave the others in the next collective); every rank takes
+        part, whatever it owns or selects.  The bad-target counter is read once per (labels, mask, ignore_index), not per step."""
+        if mask is None and weight is None and ignore_index is None and reduction == "mean":
+            out = self.forward(shard)
+            n_own = out.size(0)
+            if n_own == 0:
+                return out.sum() * 0.0
+            return self.ops.cross_entropy_mean(out, shard.y) * (n_own / shard.n_fo)
+        if reduction not in ("mean", "sum"):
+            raise ValueError(f"ShardedDBGNN.loss: reduction must be 'mean' or 'sum', got {reduction!r}")
+        if ignore_index is not None and not isinstance(ignore_index, int):
+            raise TypeError("ShardedDBGNN.loss: ignore_index must be an int or None")
+        mask = self._mask_of(shard, mask)
         out = self.forward(shard)
-        n_own = out.size(0)
-        if n_own == 0:
-            return out.sum() * 0.0
-        return self.ops.cross_entropy_mean(out, shard.y) * (n_own / shard.n_fo)
+        share, counts = _ShardedMaskedLoss.apply(out, shard.y, mask, weight, ignore_index, reduction == "mean", self.comm, self.ops)
+        from .dbgnn import _check_selected_targets
+        _check_selected_targets(counts, shard.y, mask, ignore_index, out.size(1))
+        return share
+
+    @staticmethod
+    def _mask_of(shard: DbgnnShard, mask):
+        if isinstance(mask, str):
+            if mask not in shard.masks:
+                raise KeyError(f"ShardedDBGNN: the shard carries no mask {mask!r} (it has {sorted(shard.masks)})")
+            return shard.masks[mask]
+        if mask is not None and (not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool or mask.dim() != 1 or mask.size(0) != shard.fo.n_own):
+            raise ValueError(f"ShardedDBGNN: mask must be a key of shard.masks or a bool [{shard.fo.n_own}] tensor")
+        return mask
+
+    def evaluate(self, shard: DbgnnShard, *, mask=None, ignore_index=None) -> dict:
+        """The dict of :func:`pathpyg_amd.nn.evaluate` over the selected first-order nodes of ALL ranks, identical on every rank: each rank
+        counts its rows (pp_confusion_f32), ONE all-reduce adds the ``[C * C + 1]`` counters (matrix + selected targets outside [0, C), so
+        every rank raises IndexError together), one read-back gives the scores.  A collective: every rank calls it alike.  Runs the model as
+        it stands (call ``model.eval()`` first to score without dropout)."""
+        from .dbgnn import scores_from_confusion
+        mask = self._mask_of(shard, mask)
+        with torch.no_grad():
+            out = self.forward(shard)
+        c = out.size(1)
+        buf = self.ops.confusion_counts(out, shard.y, mask, ignore_index)
+        if self.comm.world > 1:
+            self.comm.all_reduce_(buf)
+        host = buf.cpu().numpy()
+        if int(host[c * c]):
+            raise IndexError(f"evaluate: {int(host[c * c])} selected target(s) outside [0, {c})")
+        return scores_from_confusion(host[: c * c].reshape(c, c), buf[: c * c].view(c, c))
+
+
+class _ShardedMaskedLoss(torch.autograd.Function):
+    """One rank's share of the masked, class-weighted cross-entropy over the rows of all ranks.  The rank's float64 sums and its two counters
+    (``ops.masked_sums``) travel in ONE all-reduce of four float64 words (a count is exact there up to 2^53) — every rank enters it, also one
+    without rows; ``ops.masked_finish`` then rounds the GLOBAL sums once, with the single-process arithmetic.  Value: the rank's numerator
+    over the global denominator (mean; 0 / 0 = NaN on an empty global selection) or the rank's numerator (sum), so at world size 1 it is
+    ``pathpyg_amd.nn.cross_entropy`` to the bit.  Backward: the kernel's raw gradient times the global ``1 / den`` (0 on an empty selection).
+    Second output: the global counters int64 ``[2]`` (selected, out of range)."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mask, weight, ignore_index, mean: bool, comm, ops):
+        sums, counts, raw = ops.masked_sums(logits.detach(), target, mask, weight, ignore_index, ctx.needs_input_grad[0])
+        mine = sums[0].clone()
+        if comm.world > 1:
+            both = comm.all_reduce_(torch.cat((sums, counts.to(torch.float64))))
+            sums, counts = both[:2].contiguous(), both[2:].round().to(torch.int64)
+        values = ops.masked_finish(sums, counts)
+        ctx.mean = mean
+        ctx.save_for_backward(raw, values[3])
+        ctx.mark_non_differentiable(counts)
+        return ((mine / sums[1]) if mean else mine).to(torch.float32), counts
+
+    @staticmethod
+    def backward(ctx, dloss, _):
+        raw, inv_den = ctx.saved_tensors
+        return raw * (dloss * inv_den if ctx.mean else dloss), None, None, None, None, None, None, None
