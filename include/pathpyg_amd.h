@@ -410,6 +410,38 @@ int pp_time_stats(const void* time, int time_dtype, int64_t n, int64_t* out3, pp
 int pp_gather_events(const int64_t* edge_index, const void* time, const int64_t* perm, int64_t m, int64_t* edge_index_out, void* time_out,
                      int64_t* status, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ ingest of integer temporal edge lists (pp_ingest.hip) */
+
+/* read_csv_temporal_graph, src/pathpyG/io/pandas.py:511-546 (pandas.read_csv of a `v<sep>w<sep>t` file), and the three columns
+ * df_to_temporal_graph, src/pathpyG/io/pandas.py:318-397, takes from that frame — for files whose every non-blank line is exactly
+ * `[0-9]{1,18} sep [0-9]{1,18} sep -?[0-9]{1,18}`, ended by "\n", "\r\n" or the end of the file (blank lines, empty or a lone "\r",
+ * are skipped as pandas skips them; a header line is the caller's to cut off).  `bytes` is ONE CHUNK of the file on the device: it
+ * starts at a line start, ends behind a '\n' or at the end of the file, and holds n_bytes < 2^31 bytes; no byte at or past n_bytes is
+ * read.  `sep` is one ASCII byte other than a digit, '-', '\r' and '\n' (PP_ERR_ARG otherwise).
+ *
+ * pp_ingest_index writes the offset of the first byte of every non-blank line to line_start[0 .. min(n_lines, line_cap)) in file order
+ * and leaves int64 {n_lines, status, smallest offending byte offset (INT64_MAX: none), 0} at the START of the workspace.
+ * pp_ingest_parse takes that SAME workspace (it reads n_lines from it, so no read-back lies between the two calls), parses line i into
+ * v[i], w[i], t[i] (each [line_cap]) and ORs what it finds into the status.  A status other than 0 means "this file does not qualify",
+ * not an error: both calls still return PP_OK, the columns then hold unspecified values, and the caller gives the file to pandas.  One
+ * 32-byte read-back per chunk says everything.  line_cap >= (n_bytes + 1) / 6 can never be exceeded by a qualifying chunk. */
+enum pp_ingest_status {
+    PP_INGEST_BAD_BYTE = 1,     /* a byte that is neither a digit, the separator, '-', '\r' nor '\n' */
+    PP_INGEST_FIELD_COUNT = 2,  /* a line with fewer or more than three fields */
+    PP_INGEST_TOKEN_LONG = 4,   /* more than 18 digits */
+    PP_INGEST_TOKEN_EMPTY = 8,  /* an empty field, or a '-' without digits */
+    PP_INGEST_MINUS = 16,       /* a '-' anywhere but in front of the third field */
+    PP_INGEST_BAD_CR = 32,      /* a '\r' that does not stand directly before '\n' */
+    PP_INGEST_NO_LINES = 64,    /* no non-blank line at all */
+    PP_INGEST_LINE_CAP = 128    /* more than line_cap lines */
+};
+size_t pp_ingest_index_ws_bytes(int64_t n_bytes);
+int pp_ingest_index(const uint8_t* bytes, int64_t n_bytes, int sep, int32_t* line_start, int64_t line_cap, void* ws, size_t ws_bytes,
+                    pp_stream_t stream);
+size_t pp_ingest_parse_ws_bytes(int64_t n_bytes); /* == pp_ingest_index_ws_bytes: the two calls share one workspace */
+int pp_ingest_parse(const uint8_t* bytes, int64_t n_bytes, int sep, const int32_t* line_start, int64_t line_cap, int64_t* v, int64_t* w,
+                    int64_t* t, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 /* ------------------------------------------------------------------ DBGNN message passing (pp_dbgnn.hip) */
 
 /* What PyG's gcn_norm computes on every GCNConv call of DBGNN.forward (src/pathpyG/nn/dbgnn.py:133,139):

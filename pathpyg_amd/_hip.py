@@ -475,6 +475,46 @@ def argsort(keys: torch.Tensor, value_range: tuple[int, int] | None = None) -> t
     return perm
 
 
+# ------------------------------------------------------------------ ingest (csrc/pp_ingest.hip)
+INGEST_MAX_CHUNK = 0x7fffffff - 1       # pp_ingest_*: line offsets are int32
+
+
+def ingest_workspace(n_bytes: int, device) -> torch.Tensor:
+    """The workspace one :func:`ingest_index` / :func:`ingest_parse` pair shares."""
+    return _workspace(lib().pp_ingest_index_ws_bytes(int(n_bytes)), device)
+
+
+def ingest_index(chunk: torch.Tensor, sep: int, ws: torch.Tensor) -> torch.Tensor:
+    """Offsets (int32, file order) of the first byte of every non-blank line of ``chunk`` (uint8, on the device).  The vector has the
+    capacity no qualifying chunk exceeds; the line count stays on the device (in ``ws``) for :func:`ingest_parse`."""
+    dev = require_device(chunk, ws)
+    chunk = chunk.contiguous()
+    n = chunk.numel()
+    with torch.cuda.device(dev):
+        line_start = torch.empty((n + 1) // 6 + 1, dtype=torch.int32, device=dev)
+        check(lib().pp_ingest_index(_p(chunk), n, int(sep), _p(line_start), line_start.numel(), _p(ws), ws.numel(), _stream()), "pp_ingest_index")
+    return line_start
+
+
+def ingest_parse(chunk: torch.Tensor, sep: int, line_start: torch.Tensor, ws: torch.Tensor) -> torch.Tensor:
+    """``[3, capacity]`` int64: rows ``v``, ``w``, ``t``; column ``i`` is line ``i`` of :func:`ingest_index`.  Only the first
+    ``n_lines`` columns (:func:`ingest_result`) are written, and they mean something only when the status is 0."""
+    dev = require_device(chunk, line_start, ws)
+    chunk = chunk.contiguous()
+    cap = line_start.numel()
+    with torch.cuda.device(dev):
+        cols = torch.empty((3, cap), dtype=torch.int64, device=dev)
+        check(lib().pp_ingest_parse(_p(chunk), chunk.numel(), int(sep), _p(line_start), cap, _p(cols[0]), _p(cols[1]), _p(cols[2]),
+                                    _p(ws), ws.numel(), _stream()), "pp_ingest_parse")
+    return cols
+
+
+def ingest_result(ws: torch.Tensor) -> tuple[int, int, int]:
+    """``(n_lines, status, smallest offending byte offset)`` of a chunk: the one read-back of its index + parse."""
+    n_lines, status, bad_at, _ = ws[:32].view(torch.int64).tolist()
+    return n_lines, status, bad_at
+
+
 def ptr_from_sorted(sorted_index: torch.Tensor, num_rows: int) -> torch.Tensor:
     sorted_index = sorted_index.to(torch.int64).contiguous()
     dev = require_device(sorted_index)

@@ -11,17 +11,22 @@ from __future__ import annotations
 
 import ast
 import csv
+import logging
+import os
 from typing import Any, Optional
 
 import numpy as np
 import pandas as pd
 import torch
 
+from .. import _hip
 from ..core.graph import Graph
 from ..core.index_map import IndexMap
 from ..core.path_data import PathData
 from ..core.temporal_graph import TemporalGraph
 from ..data import Data
+
+_log = logging.getLogger(__name__)
 
 
 def _parse_timestamps(df: pd.DataFrame, timestamp_format: str, time_rescale: int) -> pd.Series:
@@ -198,8 +203,168 @@ def temporal_graph_to_df(graph: TemporalGraph, node_indices: Optional[bool] = Fa
     return frame
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Native ingest of integer edge lists (csrc/pp_ingest.hip): with a CUDA ``device``, a file whose every non-blank line is exactly
+# ``[0-9]{1,18} sep [0-9]{1,18} sep -?[0-9]{1,18}`` is indexed, parsed, de-duplicated and mapped to node indices on the device; only the
+# sorted node IDs come back to the host.  Every other file (and every other call) takes the pandas code below, unchanged: the kernels
+# report what disqualifies a file in a status word, nothing is raised, and pandas decides what such a file means.
+NATIVE_CSV = True          # False: read_csv_temporal_graph always takes the pandas path
+CHUNK_BYTES = 1 << 30      # the file goes to the device in pieces of at most this many bytes, each ending at a '\n' (always below 2^31)
+
+_NO_LINES = 64             # PP_INGEST_NO_LINES: a piece of blank lines only disqualifies nothing, a file without any data line does
+_SEARCH_WINDOW = 1 << 16
+
+
+def _native_sep(sep) -> int | None:
+    """The separator as a byte value when the kernels take it: one ASCII byte, no digit, ``-``, ``\\r`` or ``\\n`` (nor ``"``, which
+    pandas treats as a quote)."""
+    if not isinstance(sep, str) or len(sep) != 1 or ord(sep) >= 128 or ord(sep) == 0:
+        return None
+    if sep.isdigit() or sep in '-\r\n"':
+        return None
+    return ord(sep)
+
+
+def _header_length(head: bytes, sep: str) -> int | None:
+    """Bytes the header line takes (terminator included) when the file starts with exactly ``v<sep>w<sep>t`` + ``\\n`` / ``\\r\\n`` /
+    end of file; ``None`` for any other first line."""
+    want = f"v{sep}w{sep}t".encode()
+    if not head.startswith(want):
+        return None
+    rest = head[len(want):len(want) + 2]
+    if rest == b"":
+        return len(want)
+    if rest[:1] == b"\n":
+        return len(want) + 1
+    if rest == b"\r\n":
+        return len(want) + 2
+    return None
+
+
+def _newline_end_before(raw: np.ndarray, lo: int, hi: int) -> int:
+    """Index just behind the last ``\\n`` of ``raw[lo:hi]``, -1 if there is none (searched backwards, a window at a time)."""
+    b = hi
+    while b > lo:
+        a = max(lo, b - _SEARCH_WINDOW)
+        at = raw[a:b].tobytes().rfind(b"\n")
+        if at >= 0:
+            return a + at + 1
+        b = a
+    return -1
+
+
+def _newline_end_from(raw: np.ndarray, lo: int) -> int:
+    """Index just behind the first ``\\n`` of ``raw[lo:]``, ``len(raw)`` if there is none."""
+    n = len(raw)
+    a = lo
+    while a < n:
+        b = min(n, a + _SEARCH_WINDOW)
+        at = raw[a:b].tobytes().find(b"\n")
+        if at >= 0:
+            return a + at + 1
+        a = b
+    return n
+
+
+def _cut_chunks(raw, chunk_bytes: int, start: int = 0) -> list[tuple[int, int]]:
+    """``[(lo, hi), ...]`` covering ``raw[start:]`` in order: every piece has at most ``chunk_bytes`` bytes and ends behind a ``\\n``
+    (or at the end of the input: a last line without ``\\n`` is kept); a piece that would hold no ``\\n`` grows to the next one."""
+    if isinstance(raw, (bytes, bytearray)):
+        raw = np.frombuffer(raw, dtype=np.uint8)
+    chunk_bytes = max(1, min(int(chunk_bytes), _hip.INGEST_MAX_CHUNK))
+    n, lo, out = len(raw), start, []
+    while lo < n:
+        hi = min(lo + chunk_bytes, n)
+        if hi < n:
+            cut = _newline_end_before(raw, lo, hi)
+            hi = cut if cut > lo else _newline_end_from(raw, hi)
+        out.append((lo, hi))
+        lo = hi
+    return out
+
+
+def _first_occurrences(rows: torch.Tensor) -> torch.Tensor | None:
+    """Mask of the rows of ``rows`` [n, k] that no earlier row equals (``DataFrame.drop_duplicates`` keeps those, in order); ``None`` when
+    every row is distinct."""
+    n = rows.size(0)
+    uniq, inverse = _hip.unique_rows(rows)
+    if uniq.size(0) == n:
+        return None
+    order = _hip.argsort(inverse, (0, uniq.size(0) - 1))                    # stable: inside a group of equal rows the file order stays
+    grouped = inverse[order]
+    head = torch.ones(n, dtype=torch.bool, device=rows.device)
+    head[1:] = grouped[1:] != grouped[:-1]
+    keep = torch.zeros(n, dtype=torch.bool, device=rows.device)
+    keep[order[head]] = True
+    return keep
+
+
+def _read_csv_temporal_native(filename, sep: str, header: bool, time_rescale, multiedges: bool, num_nodes, device: torch.device):
+    """The TemporalGraph of a qualifying file, ``None`` for a file (or arguments) the native path does not take."""
+    sep_byte = _native_sep(sep)
+    if sep_byte is None or not isinstance(filename, (str, os.PathLike)) or not os.path.isfile(filename):
+        return None
+    if isinstance(time_rescale, bool) or not isinstance(time_rescale, (int, np.integer)) or time_rescale < 1:
+        return None
+    raw = np.fromfile(filename, dtype=np.uint8)
+    start = 0
+    if header:
+        start = _header_length(raw[:8].tobytes(), sep)
+        if start is None:
+            return None
+    with torch.cuda.device(device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        parts = []
+        for lo, hi in _cut_chunks(raw, CHUNK_BYTES, start):
+            if hi - lo > _hip.INGEST_MAX_CHUNK:
+                return None
+            chunk = torch.from_numpy(raw[lo:hi]).to(dev)
+            ws = _hip.ingest_workspace(hi - lo, dev)
+            line_start = _hip.ingest_index(chunk, sep_byte, ws)
+            cols = _hip.ingest_parse(chunk, sep_byte, line_start, ws)
+            n_lines, status, bad_at = _hip.ingest_result(ws)                 # the chunk's one read-back
+            if status & ~_NO_LINES:
+                _log.debug("native ingest: %s does not qualify (status %#x, byte %d): pandas reads it", filename, status, lo + bad_at)
+                return None
+            if n_lines:
+                parts.append(cols[:, :n_lines].clone())                     # (cols has the capacity of the worst case: let it go)
+            del chunk, line_start, cols, ws
+        if not parts:
+            _log.debug("native ingest: %s has no data line: pandas reads it", filename)
+            return None
+        cols = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+        del parts
+        if cols.size(1) >= 1 << 30:                                         # (the 2 n endpoints are indexed with 32 bits)
+            return None
+        v, w, t = cols[0], cols[1], cols[2]
+        if time_rescale != 1:
+            t = torch.div(t, int(time_rescale), rounding_mode="floor")
+        if not multiedges:
+            keep = _first_occurrences(torch.stack([v, w, t], dim=1))
+            if keep is not None:
+                v, w, t = v[keep], w[keep], t[keep]
+        # np.unique(df[["v", "w"]].values, return_inverse=True): sorted IDs, inverse in row-major (v0, w0, v1, w1, ...) order
+        ids, inverse = _hip.unique_rows(torch.stack([v, w], dim=1).reshape(-1, 1))
+        edge_index = inverse.view(-1, 2).t().contiguous()
+        ids = ids.view(-1).cpu().numpy()
+        data = Data(edge_index=edge_index, time=t.contiguous(), num_nodes=num_nodes if num_nodes is not None else len(ids))
+        return TemporalGraph(data=data, mapping=IndexMap(ids))
+
+
 def read_csv_temporal_graph(filename: str, sep: str = ",", header: bool = True, timestamp_format: str = "%Y-%m-%d %H:%M:%S",
                             time_rescale: int = 1, **kwargs: Any) -> TemporalGraph:
+    """Temporal graph from a ``v, w, t`` (+ edge attributes) text file.  With a CUDA ``device`` an all-integer three-column file is
+    parsed on the device (see ``NATIVE_CSV`` above); everything else goes through ``pandas.read_csv``.  Both give the same graph."""
+    if NATIVE_CSV and set(kwargs) <= {"multiedges", "num_nodes", "device"} and kwargs.get("device") is not None:
+        try:
+            device = torch.device(kwargs["device"])
+        except (RuntimeError, TypeError, ValueError):
+            device = None
+        if device is not None and device.type == "cuda":
+            g = _read_csv_temporal_native(filename, sep, header, time_rescale, bool(kwargs.get("multiedges", False)),
+                                          kwargs.get("num_nodes"), device)
+            if g is not None:
+                return g
     df = pd.read_csv(filename, header=0 if header else None, sep=sep)
     return df_to_temporal_graph(df, timestamp_format=timestamp_format, time_rescale=time_rescale, **kwargs)
 
