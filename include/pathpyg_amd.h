@@ -399,7 +399,9 @@ int pp_count_descents_f64(const double* a, int64_t n, int64_t* descents, pp_stre
 size_t pp_argsort_ws_bytes(int64_t n);
 int pp_argsort_i64(const int64_t* keys, int64_t n, int64_t min_value, int64_t max_value, int64_t* perm_out, void* ws, size_t ws_bytes,
                    pp_stream_t stream);
-/* stable replacement of torch.argsort(time) for float64 timestamps, src/pathpyG/core/temporal_graph.py:58 */
+/* stable replacement of torch.argsort(time) for float64 timestamps, src/pathpyG/core/temporal_graph.py:58.  The order of float64 values
+ * here and in pp_count_descents_f64 / pp_time_stats / the sortedness checks of the temporal builders is torch.sort's: ascending,
+ * -0.0 == 0.0, every NaN (either sign, any payload) after +inf and tied; a NaN directly before a number is a descent. */
 int pp_argsort_f64(const double* keys, int64_t n, int64_t* perm_out, void* ws, size_t ws_bytes, pp_stream_t stream);
 int pp_ptr_from_sorted_i64(const int64_t* sorted, int64_t n, int64_t num_rows, int64_t* ptr, pp_stream_t stream);
 /* TemporalGraph.__init__, src/pathpyG/core/temporal_graph.py:58-63 (argsort of the timestamps, then edge_index / time indexed by it):

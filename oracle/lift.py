@@ -127,6 +127,8 @@ def temporal_lift_sorted(edge_index: torch.Tensor, time: torch.Tensor, delta=1, 
     (stable, so ids ascend inside a group); each event looks up, inside the group
     of its head node, the ids falling into its admissible id window.
     Returns an empty ``[2,0]`` tensor when there is no pair.
+    Requires finite times and finite thresholds ``t + delta``: ``torch.searchsorted`` ranks a NaN as the largest value where the
+    reference's ``<=`` is false (tests/test_time_domain_host.py; on such streams use :func:`temporal_lift_per_timestamp`).
     """
     m = edge_index.size(1)
     tails, heads = edge_index[0], edge_index[1]

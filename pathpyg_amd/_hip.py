@@ -968,13 +968,14 @@ class MultiOrderLayer:
 
 def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int, delta, weight: torch.Tensor | None, max_order: int,
                          clock: list | None = None, event_graph: torch.Tensor | None = None, pass_instances: int = _INT32_ROWS,
-                         passes: list | None = None):
+                         passes: list | None = None, unsorted_ok: bool = False):
     """All De Bruijn layers 1..max_order of a TIME-SORTED event stream, level by level (pp_multiorder_prepare / _step, csrc/pp_multiorder.hip):
     no instance graph ``[2, E_k]``, no per-instance node sequences, no global sort beyond the two of the first order; one read-back per order.
     Returns ``[MultiOrderLayer]`` (index k - 1 = layer k; ``n_instances`` = E_k, the instance edges the reference would have lifted, a Python
     int of any size) or ``None`` when the generic kernels have to take over: a layer without edges, a node sequence with more than 4096
-    continuations (dense contact streams), a layer with 2^31 - 16 or more edges, 2^31 continuations of one first-order node pair, an
-    unsorted stream.  A level with more than ``pass_instances`` instances (at most and by default what one step numbers, 2^31 - 17) is no refusal: from there
+    continuations (dense contact streams), a layer with 2^31 - 16 or more edges, 2^31 continuations of one first-order node pair and, with
+    ``unsorted_ok``, a stream that is not sorted by time (torch.sort's order: a NaN before a number is a descent) — without it that stream
+    raises ``ValueError``, as in :func:`temporal_lift` and :func:`debruijn2`.  A level with more than ``pass_instances`` instances (at most and by default what one step numbers, 2^31 - 17) is no refusal: from there
     on every level is cut into parts of whole types of at most that many instances, the unchanged step runs on one part after another and
     the parts' pieces are joined (``core/multi_order_passes.py``: pp_multiorder_split / _concat; one read-back per part and step, one per
     split).  ``passes``: a list that receives the number of parts layer 1..max_order were built in (all ones without such a level).
@@ -1034,6 +1035,9 @@ def multi_order_temporal(edge_index: torch.Tensor, time: torch.Tensor, num_nodes
             clock.append(("prepare", t0, tick()))
         del lift_ws, ws
         _bad_index(status, "MultiOrderModel.from_temporal_graph")
+        if status & 2 and not unsorted_ok:
+            raise ValueError("lift_order_temporal: the events are not sorted by time (TemporalGraph sorts them on construction; "
+                             "data.time / data.edge_index were modified afterwards)")
         if status & (2 | 4):
             return None                  # (unsorted: the caller sorts and takes the generic path; 2^31 continuations of one node pair's events)
         if event_graph is not None and children != n_list:      # the instances of level 2 ARE the event graph's edges

@@ -800,7 +800,8 @@ def _multi_order_fused(g: TemporalGraph, delta, max_order: int, weight: str, cac
         if not isinstance(event_graph, torch.Tensor) or not event_graph.is_cuda or event_graph.dim() != 2 or event_graph.size(0) != 2:
             return None
     passes: list = []
-    built = _hip.multi_order_temporal(ei, time, n, delta, w, max_order, event_graph=event_graph, pass_instances=PASS_INSTANCES, passes=passes)
+    built = _hip.multi_order_temporal(ei, time, n, delta, w, max_order, event_graph=event_graph, pass_instances=PASS_INSTANCES, passes=passes,
+                                       unsorted_ok=True)
     if built is None:
         return None
     out = MultiOrderModel()

@@ -382,21 +382,23 @@ __global__ __launch_bounds__(kBlock) void k_count_descents(const int64_t* __rest
 }
 
 __global__ __launch_bounds__(kBlock) void k_count_descents_f64(const double* __restrict__ a, int64_t n, int64_t* __restrict__ out) {
-    // grid-stride: at most one atomic per wave of a bounded grid (an unsorted 10^7-element input used to queue 1.6*10^5 of them on one word)
+    // grid-stride: at most one atomic per wave of a bounded grid (an unsorted 10^7-element input used to queue 1.6*10^5 of them on one word);
+    // descents of torch.sort's order (pp_common.h): a NaN before a number is one
     uint32_t mine = 0;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i + 1 < n; i += (int64_t)gridDim.x * kBlock) mine += a[i] > a[i + 1] ? 1u : 0u;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i + 1 < n; i += (int64_t)gridDim.x * kBlock) mine += descends(a[i], a[i + 1]) ? 1u : 0u;
     const uint32_t total = wave_sum<uint32_t>(mine);
     if (lane_id() == 0 && total) atomicAdd((unsigned long long*)out, (unsigned long long)total);
 }
 
-// order-preserving map double -> uint64 (negative values: all bits flipped; others: sign bit set); -0.0 == +0.0
+// order-preserving map double -> uint64 (negative values: all bits flipped; others: sign bit set); -0.0 == +0.0; every NaN, whatever its
+// sign and payload, gets the ONE key above +inf's (a sign-bit NaN would otherwise land below -inf, NaNs of different payloads apart)
 __global__ __launch_bounds__(kBlock) void k_keys_from_f64(const double* __restrict__ a, int64_t n, uint64_t* __restrict__ keys) {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     double v = a[i];
     if (v == 0.0) v = 0.0;
     uint64_t b = (uint64_t)__double_as_longlong(v);
-    keys[i] = (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+    keys[i] = v != v ? ~0ull : ((b >> 63) ? ~b : (b | 0x8000000000000000ull));
 }
 
 template <typename KeyT>

@@ -283,12 +283,19 @@ __device__ __forceinline__ float4 elu_fast4(float4 v) {
     return make_float4(a[0], a[1], b[0], b[1]);
 }
 
-// first index in [lo, hi) with a[idx] > key (upper bound), a ascending
+// The timestamp order of the package is torch.sort's: ascending, -0.0 == +0.0, every NaN (either sign, any payload) after +inf and tied with
+// every other NaN.  `a` directly before `b` is a DESCENT of that order iff a > b, or a is a NaN and b is none (plain a > b is false on both
+// sides of a NaN: [5, NaN, 1] would count as sorted).  Integers: a > b.
+template <typename T>
+__device__ __forceinline__ bool descends(T a, T b) { return a > b || (a != a && b == b); }
+
+// first index in [lo, hi) with a[idx] > key (upper bound), a ascending; floating point: ascending in the order above — a NaN element lies
+// beyond every key (the test is `<=`, false on a NaN, not `>`), and a NaN key gives lo
 template <typename T, typename I>
 __device__ __forceinline__ I upper_bound_dev(const T* __restrict__ a, I lo, I hi, T key) {
     while (lo < hi) {
         I mid = lo + ((hi - lo) >> 1);
-        if (a[mid] > key) hi = mid; else lo = mid + 1;
+        if (a[mid] <= key) lo = mid + 1; else hi = mid;
     }
     return lo;
 }

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_keys(const int64_t* __restrict__
     int64_t s = ei[e], d = ei[m + e];
     if (s < 0 || s >= n || d < 0 || d >= n) { atomicOr((unsigned long long*)status, (unsigned long long)kDb2BadIndex); s = 0; d = 0; }
     const TimeT t = time[e];
-    if (e + 1 < m && time[e + 1] < t) atomicOr((unsigned long long*)status, (unsigned long long)kDb2Unsorted);
+    if (e + 1 < m && descends(t, time[e + 1])) atomicOr((unsigned long long*)status, (unsigned long long)kDb2Unsorted);
     tkeys[e] = (uint32_t)s;
     Db2Rec r;
     r.t = __builtin_bit_cast(uint64_t, t);
@@ -1319,16 +1319,21 @@ __global__ __launch_bounds__(kBlock) void k_db2_hubx(int64_t n_tasks, int64_t de
                 if (ncol > 0) {
                     const TimeT t_first = time_of<TimeT>(tms[0]), t_last = time_of<TimeT>(tms[ninst - 1]);
                     const typename W::Thr thr_last = W::threshold(t_last, delta_i, delta_f);
+                    // float64 streams end in their NaNs (torch.sort's order): a NaN out-event continues nothing and lies beyond every bound (both
+                    // tests are `<=`, false on a NaN); a piece whose LAST instance is a NaN has no last window to stop at — its numbers may reach
+                    // any out-event that is a number
+                    const bool nan_last = t_last != t_last;
                     int64_t g0 = 0, hi = no;
                     while (g0 < hi) {                                 // first out-event later than the first instance
                         const int64_t mid = g0 + ((hi - g0) >> 1);
-                        if (time_of<TimeT>(otb[mid]) > t_first) hi = mid; else g0 = mid + 1;
+                        if (time_of<TimeT>(otb[mid]) <= t_first) g0 = mid + 1; else hi = mid;
                     }
                     int64_t g1 = g0;
                     hi = no;
                     while (g1 < hi) {                                 // first one beyond the last instance's window
                         const int64_t mid = g1 + ((hi - g1) >> 1);
-                        if (!W::admits(time_of<TimeT>(otb[mid]), thr_last)) hi = mid; else g1 = mid + 1;
+                        const TimeT tm = time_of<TimeT>(otb[mid]);
+                        if (nan_last ? tm == tm : W::admits(tm, thr_last)) g1 = mid + 1; else hi = mid;
                     }
                     // the out-events ascend in time and so do the instances: ONE cursor into the LDS times follows the scan — `plo`, the first
                     // instance whose window has not ended before the batch's first out-event (its time and threshold sit in registers).  A

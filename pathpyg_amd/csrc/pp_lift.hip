@@ -103,7 +103,10 @@ __device__ __forceinline__ void list_tail(const uint32_t* __restrict__ ids_by_ta
 //   instructions touch the same 64 random lines twice), g_lo (= i + 1 without timestamp ties: probe, gallop, bisect), g_hi by bisection
 //   between the two window marks of the wave (k_window_marks: ~6 levels inside one or two cache lines all 64 lanes share instead of 23
 //   dependent levels over the stream; 0.635 -> 0.466 ms).  Every search relies on a time-sorted stream (the reference's mask loop does
-//   not, temporal.py:37-43): a descent sets a status bit instead of returning a wrong event graph.
+//   not, temporal.py:37-43): a descent sets a status bit instead of returning a wrong event graph.  Float64 streams are sorted in
+//   torch.sort's order (pp_common.h `descends`): NaNs at the end, where every comparison with them is false — they are no source (their threshold is
+//   a NaN) and no continuation (`t_j <= thr` fails); a NaN threshold (-inf + inf, delta = NaN) admits nothing.  The searches test with
+//   `<=`, which a NaN element fails, so the NaN tail reads as "beyond every key" (`!(t_j > t_i)` would take a NaN for a tie).
 // Phase B, EIGHT LANES PER EVENT: the list is short (the node's out-degree) and sits in one or two cache lines nothing else on this CU
 //   touches again.  A group of 8 lanes reads ONE aligned 128-byte line of its event's list per instruction (the wave covers 8 events at
 //   a time, 8 rounds), counts the ids below g_lo / g_hi in registers, sums over the group with 3 xor-shuffles; the first 4 continuations
@@ -136,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void k_temporal_count(const int64_t* __rest
     const int64_t ic = live ? i : m - 1;
     const TimeT ti = time[ic];
     const TimeT t_next = ic + 1 < m ? time[ic + 1] : ti;
-    if (live && t_next < ti) atomicOr((unsigned long long*)status, (unsigned long long)kUnsortedTime);
+    if (live && descends(ti, t_next)) atomicOr((unsigned long long*)status, (unsigned long long)kUnsortedTime);
     if (__ballot(source) == 0ull) {
         if (live) { first_pos[i] = 0; count[i] = 0; }
         return;
@@ -147,9 +150,9 @@ __global__ __launch_bounds__(kBlock) void k_temporal_count(const int64_t* __rest
     Bounds bounds = {0u, 0u};
     if (source && ok) bounds = *reinterpret_cast<const Bounds*>(rowptr + v);
     int64_t g_lo = ic + 1;
-    if (g_lo < m && !(t_next > ti)) {
+    if (g_lo < m && t_next <= ti) {             // (`<=`, not `!(.. > ..)`: a NaN ends the run of ties — the gallop must not stride into the NaN tail)
         int64_t step = 2;
-        while (ic + step < m && !(time[ic + step] > ti)) step <<= 1;
+        while (ic + step < m && time[ic + step] <= ti) step <<= 1;
         int64_t hi = ic + step < m ? ic + step : m;
         g_lo = upper_bound_dev<TimeT, int64_t>(time, ic + (step >> 1) + 1, hi, ti);
     }

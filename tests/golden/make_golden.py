@@ -10,7 +10,8 @@ leading zero, both restated from PyG's documentation).
 Nothing of the reference's text is written to the repo: only seeded inputs and
 the outputs the reference code produced for them.
 
-    python tests/golden/make_golden.py            # rewrites the fixtures
+    python tests/golden/make_golden.py               # rewrites reference_vectors.npz
+    python tests/golden/make_golden.py time_domain   # rewrites time_domain_vectors.npz only
 """
 from __future__ import annotations
 
@@ -161,5 +162,36 @@ def main() -> int:
     return 0
 
 
+def time_domain() -> int:
+    """tests/golden/time_domain_vectors.npz: the reference's ``lift_order_temporal`` on the time-sorted pool stream of
+    tests/time_domain_cases.py (float64 times at +-inf, signed zeros, subnormals, beyond 2^53, NaNs of both signs) for deltas whose
+    thresholds stay finite, saturate at inf and become NaN.  Same key layout as the temporal cases above; the outputs are stored as
+    int32 (event ids below 900) to keep the file small.  ``reference_vectors.npz`` is not touched."""
+    sys.path.insert(0, str(OUT.parent.parent))
+    from tests import time_domain_cases as tc
+    ref = load_reference_functions()
+    ei, t, n, _ = tc.sorted_stream(tc.pool_stream())
+    store = {}
+    for name, delta in (("pool_delta1", 1.0), ("pool_delta2p53", 2.0 ** 53), ("pool_deltainf", float("inf")), ("pool_deltanan", float("nan"))):
+        try:
+            out = ref["lift_order_temporal"](duck_temporal_graph(ei, t), delta)
+            raised = ""
+        except (RuntimeError, ValueError) as exc:      # torch.cat([]) when no pair exists (temporal.py:53)
+            out, raised = torch.empty((2, 0), dtype=torch.long), type(exc).__name__
+        store[f"temporal/{name}/raised"] = np.asarray(raised)
+        store[f"temporal/{name}/edge_index"] = ei.numpy()
+        store[f"temporal/{name}/time"] = t.numpy()
+        store[f"temporal/{name}/delta"] = np.asarray(delta)
+        store[f"temporal/{name}/delta_kind"] = np.asarray(type(delta).__name__)
+        store[f"temporal/{name}/num_nodes"] = np.asarray(n)
+        store[f"temporal/{name}/out"] = out.numpy().astype(np.int32)
+        print(f"temporal/{name}: m={ei.shape[1]} E2={out.shape[1]} {raised}")
+    path = OUT / "time_domain_vectors.npz"
+    np.savez_compressed(path, **store)
+    print("wrote", path, f"{path.stat().st_size / 1024:.0f} KiB")
+    return 0
+
+
 if __name__ == "__main__":
-    sys.exit(main())
+    # no argument: reference_vectors.npz; "time_domain": time_domain_vectors.npz alone
+    sys.exit(time_domain() if sys.argv[1:] == ["time_domain"] else main())
