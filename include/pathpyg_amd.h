@@ -435,7 +435,11 @@ enum pp_ingest_status {
     PP_INGEST_MINUS = 16,       /* a '-' anywhere but in front of the third field */
     PP_INGEST_BAD_CR = 32,      /* a '\r' that does not stand directly before '\n' */
     PP_INGEST_NO_LINES = 64,    /* no non-blank line at all */
-    PP_INGEST_LINE_CAP = 128    /* more than line_cap lines */
+    PP_INGEST_LINE_CAP = 128,   /* more than line_cap lines */
+    /* pp_ingest_tokens_* only */
+    PP_INGEST_LEADING_ZERO = 256, /* a node token of two or more digits that starts with '0' ("007" and "7" are different node IDs) */
+    PP_INGEST_BAD_WEIGHT = 512,   /* a weight token that is not (0|[1-9][0-9]*)(\.[0-9]+)? with at most 15 digits in total */
+    PP_INGEST_TOKEN_CAP = 1024    /* more than token_cap tokens */
 };
 size_t pp_ingest_index_ws_bytes(int64_t n_bytes);
 int pp_ingest_index(const uint8_t* bytes, int64_t n_bytes, int sep, int32_t* line_start, int64_t line_cap, void* ws, size_t ws_bytes,
@@ -443,6 +447,35 @@ int pp_ingest_index(const uint8_t* bytes, int64_t n_bytes, int sep, int32_t* lin
 size_t pp_ingest_parse_ws_bytes(int64_t n_bytes); /* == pp_ingest_index_ws_bytes: the two calls share one workspace */
 int pp_ingest_parse(const uint8_t* bytes, int64_t n_bytes, int sep, const int32_t* line_start, int64_t line_cap, int64_t* v, int64_t* w,
                     int64_t* t, void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* read_csv_path_data, src/pathpyG/io/pandas.py:572-599 (csv.reader of an n-gram file, ast.literal_eval of every weight), and the walk
+ * store PathData.append_walks, src/pathpyG/core/path_data.py:126-159, makes of it — for files whose every non-blank line is one walk of
+ * integer node IDs, `node (sep node)*`, with `weight` != 0 followed by `sep weight`:
+ *   node   : 0|[1-9][0-9]{0,17}                     (a leading zero disqualifies: to csv.reader "007" and "7" are different nodes)
+ *   weight : (0|[1-9][0-9]*)(\.[0-9]+)? with at most 15 digits in total, no sign, no exponent.  Its value is (double)digits / 10^f
+ *            (f fraction digits, both operands exact doubles, one IEEE division) rounded once to float32: bit for bit what
+ *            torch.tensor([ast.literal_eval(token)], dtype=torch.float) holds.
+ * Lines end with "\n", "\r\n" or the end of the file; blank lines are skipped, exactly as pp_ingest_index defines them.  A line has any
+ * number of fields, so the TOKENS are indexed, not the lines: a token starts at the first byte of every non-blank line and behind
+ * every separator byte.  `bytes`, `n_bytes`, `sep` and the chunk rules are those of pp_ingest_index.
+ *
+ * pp_ingest_tokens_index writes, in file order, token_start[t] (byte offset) and token_line[t] (rank of the token's line) for
+ * t < min(n_tokens, token_cap), and line_first_token[l] (rank of line l's first token) for l < min(n_lines, line_cap) plus one closing
+ * entry line_first_token[n_lines] = n_tokens (the array has line_cap + 1 entries).  It leaves int64 {n_lines, status, smallest
+ * offending byte offset (INT64_MAX: none), n_tokens} at the START of the workspace.
+ * pp_ingest_tokens_parse takes that SAME workspace (no read-back between the two calls) and parses one token per lane; a lane reads
+ * no byte at or past the next token's start or n_bytes.  With `weight` != 0 the last token of line l becomes weights[l] and the others
+ * nodes[t - l]; with `weight` == 0 every token is a node, nodes[t], and weights is not written.  lengths[l] = nodes of line l.
+ * nodes has token_cap entries, lengths and weights line_cap.  As with pp_ingest_parse a status other than 0 means "this file does not
+ * qualify" (both calls return PP_OK, the outputs are unspecified): an empty token, a trailing separator, a line of the weight alone,
+ * any other byte (a '.' in a node token, a space, a quote, a sign, a letter) and a '\r' not directly before '\n' all set a bit.
+ * token_cap = line_cap = n_bytes / 2 + 1 can never be exceeded by a qualifying chunk. */
+size_t pp_ingest_tokens_ws_bytes(int64_t n_bytes);
+int pp_ingest_tokens_index(const uint8_t* bytes, int64_t n_bytes, int sep, int32_t* token_start, int32_t* token_line, int64_t token_cap,
+                           int32_t* line_first_token, int64_t line_cap, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_ingest_tokens_parse(const uint8_t* bytes, int64_t n_bytes, int sep, int weight, const int32_t* token_start,
+                           const int32_t* token_line, int64_t token_cap, const int32_t* line_first_token, int64_t line_cap,
+                           int64_t* nodes, int64_t* lengths, float* weights, void* ws, size_t ws_bytes, pp_stream_t stream);
 
 /* ------------------------------------------------------------------ DBGNN message passing (pp_dbgnn.hip) */
 

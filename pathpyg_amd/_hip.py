@@ -515,6 +515,58 @@ def ingest_result(ws: torch.Tensor) -> tuple[int, int, int]:
     return n_lines, status, bad_at
 
 
+class TokenIndex(NamedTuple):
+    """What :func:`ingest_tokens_index` leaves on the device for :func:`ingest_tokens_parse` (capacities, not counts)."""
+    token_start: torch.Tensor           # [cap] int32
+    token_line: torch.Tensor            # [cap] int32
+    line_first_token: torch.Tensor      # [cap + 1] int32
+
+
+def ingest_tokens_workspace(n_bytes: int, device) -> torch.Tensor:
+    """The workspace one :func:`ingest_tokens_index` / :func:`ingest_tokens_parse` pair shares."""
+    return _workspace(lib().pp_ingest_tokens_ws_bytes(int(n_bytes)), device)
+
+
+def ingest_tokens_index(chunk: torch.Tensor, sep: int, ws: torch.Tensor) -> TokenIndex:
+    """Token index of an n-gram ``chunk`` (uint8, on the device): offset and line of every token, first token of every non-blank line,
+    all in file order.  The vectors have the capacity no qualifying chunk exceeds (``n // 2 + 1`` tokens and lines); both counts stay on
+    the device (in ``ws``) for :func:`ingest_tokens_parse`."""
+    dev = require_device(chunk, ws)
+    chunk = chunk.contiguous()
+    n = chunk.numel()
+    cap = n // 2 + 1
+    with torch.cuda.device(dev):
+        index = TokenIndex(torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                           torch.empty(cap + 1, dtype=torch.int32, device=dev))
+        check(lib().pp_ingest_tokens_index(_p(chunk), n, int(sep), _p(index.token_start), _p(index.token_line), cap,
+                                           _p(index.line_first_token), cap, _p(ws), ws.numel(), _stream()), "pp_ingest_tokens_index")
+    return index
+
+
+def ingest_tokens_parse(chunk: torch.Tensor, sep: int, weight: bool, index: TokenIndex, ws: torch.Tensor):
+    """``(nodes int64, lengths int64, weights float32 | None)`` at the capacity of ``index``: the node IDs of all walks in file order, the
+    nodes per walk, and (``weight``) the last token of every line.  Only the first ``n_tokens - n_lines`` (``weight``) or ``n_tokens``
+    nodes and the first ``n_lines`` lengths and weights (:func:`ingest_tokens_result`) are written, and they mean something only when the
+    status is 0."""
+    dev = require_device(chunk, ws, *index)
+    chunk = chunk.contiguous()
+    cap = index.token_start.numel()
+    with torch.cuda.device(dev):
+        nodes = torch.empty(cap, dtype=torch.int64, device=dev)
+        lengths = torch.empty(cap, dtype=torch.int64, device=dev)
+        weights = torch.empty(cap, dtype=torch.float32, device=dev) if weight else None
+        check(lib().pp_ingest_tokens_parse(_p(chunk), chunk.numel(), int(sep), 1 if weight else 0, _p(index.token_start), _p(index.token_line), cap,
+                                           _p(index.line_first_token), cap, _p(nodes), _p(lengths), _p(weights), _p(ws), ws.numel(), _stream()),
+              "pp_ingest_tokens_parse")
+    return nodes, lengths, weights
+
+
+def ingest_tokens_result(ws: torch.Tensor) -> tuple[int, int, int, int]:
+    """``(n_lines, n_tokens, status, smallest offending byte offset)`` of a chunk: the one read-back of its index + parse."""
+    n_lines, status, bad_at, n_tokens = ws[:32].view(torch.int64).tolist()
+    return n_lines, n_tokens, status, bad_at
+
+
 def ptr_from_sorted(sorted_index: torch.Tensor, num_rows: int) -> torch.Tensor:
     sorted_index = sorted_index.to(torch.int64).contiguous()
     dev = require_device(sorted_index)

@@ -12,6 +12,11 @@
 // Only files of the exact shape `[0-9]{1,18} sep [0-9]{1,18} sep -?[0-9]{1,18}` per line qualify ('\r' directly before '\n' and blank lines
 // are allowed).  Anything else is NOT an error of these kernels: they set a bit of the status word and record the smallest offending byte
 // offset; the caller then hands the file to pandas, whose type inference decides what such a file means.
+//
+// Second half of the file: integer n-gram path files (one walk per line, `node sep node ... [sep weight]`) -> nodes, lengths, weights.
+//   read_csv_path_data                   src/pathpyG/io/pandas.py:572-599   (csv.reader of the file, ast.literal_eval of every weight)
+//   PathData.append_walks                src/pathpyG/core/path_data.py:126-159
+// The same two steps with TOKENS in place of lines (a walk may be thousands of nodes long): a token index, then one lane per token.
 #include "pp_internal.h"
 
 namespace pp {
@@ -172,6 +177,178 @@ static bool ingest_sep_ok(int sep) {
     return sep > 0 && sep < 128 && !(sep >= '0' && sep <= '9') && sep != '-' && sep != '\r' && sep != '\n';
 }
 
+// ======================================================================================================================================
+// n-gram path files: one walk per line, any number of fields, so the TOKENS are indexed (one lane per line would leave a wave waiting for
+// its longest walk).  Same two steps: count / exclusive_scan / fill over 16-byte lanes, then one lane per token.
+constexpr int kIngestWeightDigits = 15;                     // 10^15 < 2^53: the digits of a weight and the power of ten are exact doubles
+
+struct IngestTokWs {
+    int64_t* result;          // {n_lines, status, smallest offending byte offset (INT64_MAX: none), n_tokens}
+    int32_t* line_count;      // [tiles]
+    int32_t* line_base;       // [tiles + 1]
+    int32_t* token_count;     // [tiles]
+    int32_t* token_base;      // [tiles + 1]
+    void* scratch;
+    size_t scratch_bytes;
+    size_t total_bytes;
+};
+
+static IngestTokWs carve_ingest_tokens(void* ws, int64_t n_bytes) {
+    Arena a(ws, (size_t)-1);
+    IngestTokWs w;
+    const int64_t tiles = ceil_div(n_bytes > 0 ? n_bytes : 1, kIngestTile);
+    w.result = a.take<int64_t>(4);
+    w.line_count = a.take<int32_t>(tiles);
+    w.line_base = a.take<int32_t>(tiles + 1);
+    w.token_count = a.take<int32_t>(tiles);
+    w.token_base = a.take<int32_t>(tiles + 1);
+    w.scratch_bytes = scan_ws_bytes(tiles);
+    w.scratch = a.take<char>((int64_t)w.scratch_bytes);
+    w.total_bytes = a.used;
+    return w;
+}
+
+// bit k set: byte base + k (< n) stands directly behind a separator byte.  No byte at or past n is read.
+__device__ __forceinline__ uint32_t behind_sep_mask(const uint8_t* __restrict__ buf, int64_t n, int64_t base, uint8_t sep, bool aligned) {
+    if (base >= n) return 0u;
+    uint8_t c[kIngestLaneBytes];                           // c[k] = the byte in front of byte base + k
+    c[0] = base > 0 ? buf[base - 1] : (uint8_t)'\n';
+    if (aligned && base + kIngestLaneBytes <= n) {
+        const uint4 q = *reinterpret_cast<const uint4*>(buf + base);
+        const uint32_t word[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int k = 0; k + 1 < kIngestLaneBytes; ++k) c[1 + k] = (uint8_t)(word[k >> 2] >> (8 * (k & 3)));
+    } else {
+#pragma unroll
+        for (int k = 0; k + 1 < kIngestLaneBytes; ++k) c[1 + k] = base + k < n ? buf[base + k] : (uint8_t)'\n';
+    }
+    uint32_t mask = 0u;
+#pragma unroll
+    for (int k = 0; k < kIngestLaneBytes; ++k)
+        if (c[k] == sep && base + k < n) mask |= 1u << k;
+    return mask;
+}
+
+// ---- pass 1: line starts and token starts per workgroup -------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_ingest_tok_count(const uint8_t* __restrict__ buf, int64_t n, uint8_t sep,
+                                                            int32_t* __restrict__ line_count, int32_t* __restrict__ token_count) {
+    __shared__ int32_t part[2][kWavesPerBlock];
+    const int64_t base = (int64_t)blockIdx.x * kIngestTile + (int64_t)threadIdx.x * kIngestLaneBytes;
+    const bool aligned = ((uintptr_t)buf & 15) == 0;
+    const uint32_t lines = line_start_mask(buf, n, base, aligned);
+    const uint32_t tokens = lines | behind_sep_mask(buf, n, base, sep, aligned);
+    const int32_t sl = wave_sum((int32_t)__popc(lines)), stk = wave_sum((int32_t)__popc(tokens));
+    if (lane_id() == 0) { part[0][wave_id()] = sl; part[1][wave_id()] = stk; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int32_t a = 0, b = 0;
+#pragma unroll
+        for (int w = 0; w < kWavesPerBlock; ++w) { a += part[0][w]; b += part[1][w]; }
+        line_count[blockIdx.x] = a;
+        token_count[blockIdx.x] = b;
+    }
+}
+
+// ---- pass 2: the token offsets, every token's line, every line's first token, in file order -------
+__global__ __launch_bounds__(kBlock) void k_ingest_tok_fill(const uint8_t* __restrict__ buf, int64_t n, uint8_t sep,
+                                                           const int32_t* __restrict__ line_base, const int32_t* __restrict__ token_base,
+                                                           int32_t* __restrict__ token_start, int32_t* __restrict__ token_line, int64_t token_cap,
+                                                           int32_t* __restrict__ line_first_token, int64_t line_cap, int64_t* __restrict__ result) {
+    __shared__ int32_t scratch[kWavesPerBlock + 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {             // (result[0] and result[3] are the scans' totals: written by earlier kernels of the stream)
+        const int64_t lines = result[0], tokens = result[3];
+        if (lines == 0) ingest_flag(result, PP_INGEST_NO_LINES, 0);
+        if (lines > line_cap) ingest_flag(result, PP_INGEST_LINE_CAP, 0);
+        if (tokens > token_cap) ingest_flag(result, PP_INGEST_TOKEN_CAP, 0);
+        if (lines <= line_cap) line_first_token[lines] = (int32_t)tokens;      // the closing entry (line_first_token has line_cap + 1)
+    }
+    const int64_t base = (int64_t)blockIdx.x * kIngestTile + (int64_t)threadIdx.x * kIngestLaneBytes;
+    const bool aligned = ((uintptr_t)buf & 15) == 0;
+    const uint32_t lines = line_start_mask(buf, n, base, aligned);
+    uint32_t tokens = lines | behind_sep_mask(buf, n, base, sep, aligned);
+    int32_t tot;
+    int64_t line_at = (int64_t)line_base[blockIdx.x] + block_exclusive_sum((int32_t)__popc(lines), scratch, &tot);
+    int64_t token_at = (int64_t)token_base[blockIdx.x] + block_exclusive_sum((int32_t)__popc(tokens), scratch, &tot);
+    while (tokens) {
+        const int k = __ffs((int)tokens) - 1;
+        if (lines >> k & 1u) {
+            if (line_at < line_cap) line_first_token[line_at] = (int32_t)token_at;
+            ++line_at;
+        }
+        if (token_at < token_cap) {
+            token_start[token_at] = (int32_t)(base + k);
+            token_line[token_at] = (int32_t)(line_at - 1);  // (a separator stands on a non-blank line, whose start lies in front of it)
+        }
+        ++token_at;
+        tokens &= tokens - 1u;
+    }
+}
+
+// ---- parse: one lane per token ----------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_ingest_tok_parse(const uint8_t* __restrict__ buf, int64_t n, uint8_t sep, int weight,
+                                                            const int32_t* __restrict__ token_start, const int32_t* __restrict__ token_line,
+                                                            const int32_t* __restrict__ line_first_token, int64_t* __restrict__ result,
+                                                            int64_t* __restrict__ nodes, int64_t* __restrict__ lengths, float* __restrict__ weights) {
+    // (the three bits are final before this kernel starts: the index step of the same stream sets them)
+    if (result[1] & (PP_INGEST_NO_LINES | PP_INGEST_LINE_CAP | PP_INGEST_TOKEN_CAP)) return;
+    constexpr double kPow10[kIngestWeightDigits + 1] = {1e0, 1e1, 1e2, 1e3, 1e4, 1e5, 1e6, 1e7, 1e8, 1e9, 1e10, 1e11, 1e12, 1e13, 1e14, 1e15};
+    const int64_t n_lines = result[0], n_tokens = result[3];
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x; t < n_tokens; t += stride) {
+        const int64_t start = token_start[t];
+        int64_t end = t + 1 < n_tokens ? (int64_t)token_start[t + 1] : n;      // behind the token's own end only blank lines follow up to `end`
+        if (end > n) end = n;
+        const int64_t line = token_line[t];
+        if (line < 0 || line >= n_lines) { ingest_flag(result, PP_INGEST_FIELD_COUNT, start); continue; }
+        int64_t val = 0, bad_at = -1, bad = 0, dot_at = -1;
+        int ndig = 0, nfrac = 0;
+        bool lead0 = false, last = true;                    // last token of its line: ended by '\r', '\n' or the end of the buffer
+        for (int64_t p = start; p < end; ++p) {
+            const uint8_t c = buf[p];
+            if (c >= '0' && c <= '9') {
+                if (ndig == kIngestMaxDigits) { bad = PP_INGEST_TOKEN_LONG; bad_at = p; break; }
+                if (ndig == 1 && val == 0 && dot_at < 0) lead0 = true;
+                val = val * 10 + (c - '0');
+                ++ndig;
+                if (dot_at >= 0) ++nfrac;
+            } else if (c == sep) {                          // (the next token starts at p + 1 == end; at the end of the buffer nothing does)
+                last = false;
+                if (p + 1 >= n) { bad = PP_INGEST_TOKEN_EMPTY; bad_at = p; }
+                break;
+            } else if (c == '\n') {
+                break;
+            } else if (c == '\r') {                        // only directly before '\n'
+                if (p + 1 >= end || buf[p + 1] != '\n') { bad = PP_INGEST_BAD_CR; bad_at = p; }
+                break;
+            } else if (c == '.') {                         // only in a weight, once, behind a digit: judged when the token's role is known
+                if (dot_at >= 0 || ndig == 0) { bad = PP_INGEST_BAD_BYTE; bad_at = p; break; }
+                dot_at = p;
+            } else {
+                bad = PP_INGEST_BAD_BYTE; bad_at = p; break;
+            }
+        }
+        if (!bad && ndig == 0) { bad = PP_INGEST_TOKEN_EMPTY; bad_at = start; }
+        const bool is_weight = weight != 0 && last;
+        if (!bad) {
+            if (is_weight) {
+                if (ndig > kIngestWeightDigits || lead0 || (dot_at >= 0 && nfrac == 0)) { bad = PP_INGEST_BAD_WEIGHT; bad_at = start; }
+            } else if (dot_at >= 0) {
+                bad = PP_INGEST_BAD_BYTE; bad_at = dot_at;
+            } else if (lead0) {
+                bad = PP_INGEST_LEADING_ZERO; bad_at = start;
+            }
+        }
+        if (!bad && (int64_t)line_first_token[line] == t) {  // the line's first token also answers for the line
+            const int64_t fields = (int64_t)line_first_token[line + 1] - t;
+            if (weight != 0 && fields < 2) { bad = PP_INGEST_FIELD_COUNT; bad_at = start; }
+            else lengths[line] = fields - (weight != 0 ? 1 : 0);
+        }
+        if (bad) { ingest_flag(result, bad, bad_at); continue; }
+        if (is_weight) weights[line] = (float)((double)val / kPow10[nfrac]);   // one correctly rounded division, one rounding to float32
+        else nodes[weight != 0 ? t - line : t] = val;
+    }
+}
+
 }  // namespace pp
 
 using namespace pp;
@@ -214,6 +391,51 @@ int pp_ingest_parse(const uint8_t* bytes, int64_t n_bytes, int sep, const int32_
     int64_t g = ceil_div(line_cap, kBlock);
     if (g > kMaxGrid) g = kMaxGrid;
     k_ingest_parse<<<(unsigned)g, kBlock, 0, st>>>(bytes, n_bytes, (uint8_t)sep, line_start, line_cap, ws_.result, v, w, t);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+size_t pp_ingest_tokens_ws_bytes(int64_t n_bytes) { return carve_ingest_tokens(nullptr, n_bytes).total_bytes; }
+
+int pp_ingest_tokens_index(const uint8_t* bytes, int64_t n_bytes, int sep, int32_t* token_start, int32_t* token_line, int64_t token_cap,
+                           int32_t* line_first_token, int64_t line_cap, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(n_bytes >= 0 && token_cap >= 0 && line_cap >= 0, PP_ERR_ARG, "pp_ingest_tokens_index: negative size");
+    PP_REQUIRE(n_bytes < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_ingest_tokens_index: a chunk of 2^31 bytes or more (%lld)", (long long)n_bytes);
+    PP_REQUIRE(ingest_sep_ok(sep), PP_ERR_ARG, "pp_ingest_tokens_index: separator %d is not one ASCII byte other than a digit, '-', CR and LF", sep);
+    IngestTokWs w = carve_ingest_tokens(ws, n_bytes);
+    PP_REQUIRE(ws_bytes >= w.total_bytes, PP_ERR_WORKSPACE, "pp_ingest_tokens_index: workspace too small");
+    k_ingest_init<<<1, 1, 0, st>>>(w.result, n_bytes == 0 ? (int64_t)PP_INGEST_NO_LINES : 0);
+    PP_LAUNCH_CHECK();
+    if (n_bytes == 0) return PP_OK;
+    const int64_t tiles = ceil_div(n_bytes, kIngestTile);
+    k_ingest_tok_count<<<(unsigned)tiles, kBlock, 0, st>>>(bytes, n_bytes, (uint8_t)sep, w.line_count, w.token_count);
+    PP_LAUNCH_CHECK();
+    int rc = exclusive_scan<int32_t, int32_t>(w.line_count, tiles, w.line_base, true, w.result, w.scratch, w.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    rc = exclusive_scan<int32_t, int32_t>(w.token_count, tiles, w.token_base, true, w.result + 3, w.scratch, w.scratch_bytes, st);
+    if (rc != PP_OK) return rc;
+    k_ingest_tok_fill<<<(unsigned)tiles, kBlock, 0, st>>>(bytes, n_bytes, (uint8_t)sep, w.line_base, w.token_base, token_start, token_line,
+                                                         token_cap, line_first_token, line_cap, w.result);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_ingest_tokens_parse(const uint8_t* bytes, int64_t n_bytes, int sep, int weight, const int32_t* token_start,
+                           const int32_t* token_line, int64_t token_cap, const int32_t* line_first_token, int64_t line_cap,
+                           int64_t* nodes, int64_t* lengths, float* weights, void* ws, size_t ws_bytes, pp_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    PP_REQUIRE(n_bytes >= 0 && token_cap >= 0 && line_cap >= 0, PP_ERR_ARG, "pp_ingest_tokens_parse: negative size");
+    PP_REQUIRE(n_bytes < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_ingest_tokens_parse: a chunk of 2^31 bytes or more (%lld)", (long long)n_bytes);
+    PP_REQUIRE(ingest_sep_ok(sep), PP_ERR_ARG, "pp_ingest_tokens_parse: separator %d is not one ASCII byte other than a digit, '-', CR and LF", sep);
+    PP_REQUIRE(weight == 0 || weights != nullptr, PP_ERR_ARG, "pp_ingest_tokens_parse: weight column asked for without a weights buffer");
+    IngestTokWs w = carve_ingest_tokens(ws, n_bytes);
+    PP_REQUIRE(ws_bytes >= w.total_bytes, PP_ERR_WORKSPACE, "pp_ingest_tokens_parse: workspace too small");
+    if (n_bytes == 0 || token_cap == 0 || line_cap == 0) return PP_OK;
+    int64_t g = ceil_div(token_cap < n_bytes ? token_cap : n_bytes, kBlock);
+    if (g > kMaxGrid) g = kMaxGrid;
+    k_ingest_tok_parse<<<(unsigned)g, kBlock, 0, st>>>(bytes, n_bytes, (uint8_t)sep, weight, token_start, token_line, line_first_token, w.result,
+                                                      nodes, lengths, weights);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

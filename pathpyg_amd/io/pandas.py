@@ -208,7 +208,10 @@ def temporal_graph_to_df(graph: TemporalGraph, node_indices: Optional[bool] = Fa
 # ``[0-9]{1,18} sep [0-9]{1,18} sep -?[0-9]{1,18}`` is indexed, parsed, de-duplicated and mapped to node indices on the device; only the
 # sorted node IDs come back to the host.  Every other file (and every other call) takes the pandas code below, unchanged: the kernels
 # report what disqualifies a file in a status word, nothing is raised, and pandas decides what such a file means.
-NATIVE_CSV = True          # False: read_csv_temporal_graph always takes the pandas path
+#
+# read_csv_path_data has the same arrangement for n-gram files of integer node IDs (the pp_ingest_tokens_* half of that file): tokens, not
+# lines, are indexed and parsed on the device, and every other file takes the csv.reader code of that function, unchanged.
+NATIVE_CSV = True          # False: read_csv_temporal_graph always takes the pandas path, read_csv_path_data always its csv.reader code
 CHUNK_BYTES = 1 << 30      # the file goes to the device in pieces of at most this many bytes, each ending at a '\n' (always below 2^31)
 
 _NO_LINES = 64             # PP_INGEST_NO_LINES: a piece of blank lines only disqualifies nothing, a file without any data line does
@@ -374,8 +377,85 @@ def write_csv(graph, node_indices: bool = False, path_or_buf: Any = None, **pdar
     frame.to_csv(index=False, path_or_buf=path_or_buf, **pdargs)
 
 
+def _string_order(ids: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Distinct non-negative integer IDs -> ``(node_ids, rank)``: the IDs as the strings the file held (no leading zeros, dtype
+    ``<U{longest}``), sorted as ``np.unique`` sorts strings (code points: ``'10' < '2'``), and ``rank[j]`` = index of ``ids[j]`` in it."""
+    ids = np.asarray(ids, dtype=np.int64)
+    width = max(len(str(int(ids.max()))), 1) if ids.size else 1
+    strings = ids.astype(f"<U{width}")
+    order = np.argsort(strings, kind="stable")
+    rank = np.empty(len(ids), dtype=np.int64)
+    rank[order] = np.arange(len(ids), dtype=np.int64)
+    return strings[order], rank
+
+
+def _read_csv_paths_native(path_or_buf, weight: bool, sep, device: torch.device) -> PathData | None:
+    """The PathData of a qualifying integer n-gram file (csrc/pp_ingest.hip, the pp_ingest_tokens_* half), ``None`` for a file (or
+    arguments) the native path does not take: the caller's host code then reads it.  Node IDs come out as the host code makes them:
+    strings in ``np.unique`` order."""
+    sep_byte = _native_sep(sep)
+    if sep_byte is None or device.type != "cuda" or not isinstance(path_or_buf, (str, os.PathLike)) or not os.path.isfile(path_or_buf):
+        return None
+    weight = bool(weight)
+    raw = np.fromfile(path_or_buf, dtype=np.uint8)
+    with torch.cuda.device(device):
+        dev = torch.device("cuda", torch.cuda.current_device())
+        parts = []
+        for lo, hi in _cut_chunks(raw, CHUNK_BYTES):
+            if hi - lo > _hip.INGEST_MAX_CHUNK:
+                return None
+            chunk = torch.from_numpy(raw[lo:hi]).to(dev)
+            ws = _hip.ingest_tokens_workspace(hi - lo, dev)
+            index = _hip.ingest_tokens_index(chunk, sep_byte, ws)
+            nodes, lengths, weights = _hip.ingest_tokens_parse(chunk, sep_byte, weight, index, ws)
+            n_lines, n_tokens, status, bad_at = _hip.ingest_tokens_result(ws)          # the chunk's one read-back
+            if status & ~_NO_LINES:
+                _log.debug("native ingest: %s does not qualify (status %#x, byte %d): the host code reads it", path_or_buf, status, lo + bad_at)
+                return None
+            if n_lines:                                                     # (the outputs have the capacity of the worst case: let them go)
+                parts.append((nodes[:n_tokens - n_lines if weight else n_tokens].clone(), lengths[:n_lines].clone(),
+                              weights[:n_lines].clone() if weight else None))
+            del chunk, ws, index, nodes, lengths, weights
+        if not parts:
+            _log.debug("native ingest: %s has no data line: the host code reads it", path_or_buf)
+            return None
+        nodes = parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts])
+        lengths = parts[0][1] if len(parts) == 1 else torch.cat([p[1] for p in parts])
+        if weight:
+            weights = parts[0][2] if len(parts) == 1 else torch.cat([p[2] for p in parts])
+        else:
+            weights = torch.ones(lengths.numel(), dtype=torch.float32, device=dev)
+        del parts
+        positions = nodes.numel()
+        if positions >= 1 << 31:
+            return None
+        # np.unique(np.hstack(paths)) of the host code: the distinct IDs AS STRINGS, in string order
+        ids, inverse = _hip.unique_rows(nodes.view(-1, 1))
+        node_ids, rank = _string_order(ids.view(-1).cpu().numpy())
+        node_idx = torch.from_numpy(rank).to(dev)[inverse]
+        # PathData.append_walks from here on, on device tensors: every position but a walk's last one starts an edge
+        pos = torch.arange(positions, device=dev)
+        last_of_walk = torch.zeros(positions, dtype=torch.bool, device=dev)
+        last_of_walk[torch.cumsum(lengths, 0) - 1] = True
+        tails = pos[~last_of_walk]
+        out = PathData(IndexMap(node_ids), dev)
+        out._append(torch.stack((tails, tails + 1)), node_idx.unsqueeze(1), weights, lengths)
+        return out
+
+
 def read_csv_path_data(path_or_buf: Any = None, weight: bool = True, sep=",", device: Optional[torch.device] = None) -> PathData:
-    """Walks from an n-gram file: one walk per line, node IDs separated by ``sep``, optionally a trailing weight."""
+    """Walks from an n-gram file: one walk per line, node IDs separated by ``sep``, optionally a trailing weight.  With a CUDA
+    ``device`` a file of integer IDs (and plain decimal weights) is indexed and parsed on the device (see ``NATIVE_CSV`` above);
+    everything else is read by the host code below.  Both give the same walk store."""
+    if NATIVE_CSV and device is not None:
+        try:
+            dev = torch.device(device)
+        except (RuntimeError, TypeError, ValueError):
+            dev = None
+        if dev is not None and dev.type == "cuda":
+            paths_native = _read_csv_paths_native(path_or_buf, weight, sep, dev)
+            if paths_native is not None:
+                return paths_native
     with open(path_or_buf, "r") as fh:
         rows = [r for r in csv.reader(fh, delimiter=sep) if r]
     if weight:
