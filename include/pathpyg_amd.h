@@ -873,6 +873,38 @@ size_t pp_mon_zeroth_llh_ws_bytes(int64_t positions, int64_t walks, int64_t n);
 int pp_mon_zeroth_llh_f64(const int64_t* node_sequence, int64_t positions, const int64_t* dag_num_nodes, const float* dag_weight, int64_t walks,
                           int64_t n, double* out2, int64_t* status, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ rolling time windows (pp_rolling.hip) */
+/* The weighted static graph of EVERY window [start_w, end_w) of a time-sorted event stream (reference RollingTimeWindow,
+ * src/pathpyG/algorithms/rolling_time_window.py:50-61: one TemporalGraph.to_static_graph(weighted=True, time_window=...) per window),
+ * from one grouping of the stream.  edge_index [2, m] int64 row-major, time [m] int64 (time_dtype 1) or float64 (3), m < 2^31 - 16.
+ *
+ * pp_rolling_group: keys_out [m] = src << bits | dst of every event, ascending (bits = significant bits of num_nodes - 1; elements of
+ *   pp_rolling_key_bytes(num_nodes) = 4 or 8 bytes), perm_out [m] the event (= time rank) at every position, stable: a node pair's events
+ *   are one run of positions in time order.  flags [1]: bit 0 a node index outside [0, num_nodes), bit 1 the stream is not in timestamp
+ *   order or holds a NaN.  With a flag set the other outputs are unspecified.  ws: pp_rolling_group_ws_bytes(m, num_nodes).
+ * pp_rolling_bounds: lo[w] / hi[w] = first event with time >= starts[w] / >= ends[w] (m when there is none), starts / ends [W] in the dtype
+ *   of `time`, W < 2^31 - 16.  Window w holds the events lo[w] <= e < hi[w].  starts and ends must be non-decreasing in w.
+ * pp_rolling_count, for the windows w0 <= w < w1: cnt[j] = number of those windows in which position j is the first position of its pair
+ *   whose event lies in the window.  report [w1 - w0 + 2] int32: report[k] - for k <= w1 - w0 - the difference array of the per-window
+ *   edge counts (edges of window w0 + k = report[0] + ... + report[k]; the whole array sums to 0), report[w1 - w0 + 1] = flags[0], plus
+ *   bit 2 when a pair has max_run events or more (max_run >= 1).
+ * pp_rolling_fill, same windows, cnt as pp_rolling_count left it and total = the sum of cnt (< 2^31 - 16): the edges of the windows one
+ *   window after the other, (src, dst)-sorted inside a window, to out_src / out_dst [total] int64 and out_weight [total] float32 (the
+ *   number of the pair's events in the window); num_nodes_out [w1 - w0] int32 = 1 + the largest node index of the window, 0 for an empty
+ *   one.  ws: pp_rolling_fill_ws_bytes(m, total). */
+int pp_rolling_key_bytes(int64_t num_nodes);
+size_t pp_rolling_group_ws_bytes(int64_t m, int64_t num_nodes);
+int pp_rolling_group(const int64_t* edge_index, const void* time, int time_dtype, int64_t m, int64_t num_nodes, void* keys_out,
+                     uint32_t* perm_out, int32_t* flags, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_rolling_bounds(const void* time, int time_dtype, int64_t m, const void* starts, const void* ends, int64_t W, int32_t* lo, int32_t* hi,
+                      pp_stream_t stream);
+int pp_rolling_count(const void* keys, int key_bytes, const uint32_t* perm, int64_t m, const int32_t* lo, const int32_t* hi, int64_t W,
+                     int64_t w0, int64_t w1, int64_t max_run, const int32_t* flags, int32_t* cnt, int32_t* report, pp_stream_t stream);
+size_t pp_rolling_fill_ws_bytes(int64_t m, int64_t total);
+int pp_rolling_fill(const void* keys, int key_bytes, const uint32_t* perm, int64_t m, int64_t num_nodes, const int32_t* lo, const int32_t* hi,
+                    int64_t W, int64_t w0, int64_t w1, const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight,
+                    int32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2225,3 +2225,92 @@ def mon_zeroth_llh(node_sequence: torch.Tensor, dag_num_nodes: torch.Tensor, dag
     if int(host[2:].view(torch.int64)) != 0:
         return None
     return float(host[0]), float(host[1])
+
+
+# ------------------------------------------------------------------ rolling time windows (csrc/pp_rolling.hip)
+ROLLING_BAD_INDEX, ROLLING_BAD_ORDER, ROLLING_LONG_RUN = 1, 2, 4       # status bits of rolling_count's report
+
+
+def rolling_key_dtype(num_nodes: int) -> torch.dtype:
+    """dtype of the ``src << bits | dst`` keys of a graph of ``num_nodes`` nodes: int32 while both indices fit 16 bits, int64 beyond."""
+    return torch.int32 if 2 * max(int(max(num_nodes, 2) - 1).bit_length(), 1) <= 32 else torch.int64
+
+
+def rolling_group(edge_index: torch.Tensor, time: torch.Tensor, num_nodes: int):
+    """``(keys, perm, flags)`` of a time-sorted stream (pp_rolling_group): the pair keys ascending, the event at every position (stable, so
+    a pair's events are one run in time order) and the flag word [1] (bit 0 an index outside [0, num_nodes), bit 1 not time-sorted or a NaN),
+    which stays on the device: :func:`rolling_count` hands it back with its report."""
+    ei = _edge_index(edge_index)
+    dev = require_device(ei, time)
+    time, _ = _event_stream(ei, time)
+    m, num_nodes = ei.size(1), int(num_nodes)
+    L = lib()
+    with torch.cuda.device(dev):
+        keys = torch.empty(m, dtype=rolling_key_dtype(num_nodes), device=dev)
+        perm = torch.empty(m, dtype=torch.int32, device=dev)
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pp_rolling_group_ws_bytes(m, num_nodes), dev)
+        check(L.pp_rolling_group(_p(ei), _p(time), _DTYPE_CODE[time.dtype], m, num_nodes, _p(keys), _p(perm), _p(flags), _p(ws), ws.numel(),
+                                 _stream()), "pp_rolling_group")
+    return keys, perm, flags
+
+
+def rolling_bounds(time: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor):
+    """``(lo, hi)`` int32 [W]: the first event with ``time >= starts[w]`` / ``>= ends[w]`` of a sorted int64 or float64 ``time``
+    (pp_rolling_bounds); ``starts`` / ``ends`` in the dtype of ``time``, non-decreasing."""
+    dev = require_device(time, starts, ends)
+    if time.dtype not in (torch.int64, torch.float64) or starts.dtype != time.dtype or ends.dtype != time.dtype:
+        raise TypeError("rolling_bounds: time, starts and ends must share the dtype int64 or float64")
+    time, starts, ends = time.contiguous(), starts.contiguous(), ends.contiguous()
+    W = starts.numel()
+    if ends.numel() != W:
+        raise ValueError("rolling_bounds: one start and one end per window")
+    with torch.cuda.device(dev):
+        lo = torch.empty(W, dtype=torch.int32, device=dev)
+        hi = torch.empty(W, dtype=torch.int32, device=dev)
+        check(lib().pp_rolling_bounds(_p(time), _DTYPE_CODE[time.dtype], time.numel(), _p(starts), _p(ends), W, _p(lo), _p(hi), _stream()),
+              "pp_rolling_bounds")
+    return lo, hi
+
+
+def rolling_count(keys: torch.Tensor, perm: torch.Tensor, lo: torch.Tensor, hi: torch.Tensor, w0: int, w1: int, max_run: int,
+                  flags: torch.Tensor):
+    """``(cnt, report)`` for the windows ``w0 .. w1 - 1`` (pp_rolling_count): ``cnt`` int32 [m] the number of those windows in which a position
+    heads its pair, ``report`` int32 [w1 - w0 + 2] the difference array of the per-window edge counts followed by the status word
+    (``flags`` plus ROLLING_LONG_RUN when a pair has ``max_run`` events or more).  Nothing is read back here."""
+    dev = require_device(keys, perm, lo, hi, flags)
+    m, W = keys.numel(), lo.numel()
+    with torch.cuda.device(dev):
+        cnt = torch.empty(m, dtype=torch.int32, device=dev)
+        report = torch.empty(w1 - w0 + 2, dtype=torch.int32, device=dev)
+        check(lib().pp_rolling_count(_p(keys), keys.element_size(), _p(perm), m, _p(lo), _p(hi), W, int(w0), int(w1), int(max_run), _p(flags),
+                                     _p(cnt), _p(report), _stream()), "pp_rolling_count")
+    return cnt, report
+
+
+def rolling_fill(keys: torch.Tensor, perm: torch.Tensor, num_nodes: int, lo: torch.Tensor, hi: torch.Tensor, w0: int, w1: int,
+                 cnt: torch.Tensor, total: int, out: tuple | None = None):
+    """``(edge_index [2, total], edge_weight [total], num_nodes [w1 - w0] int32)`` of the windows ``w0 .. w1 - 1``, window after window and
+    (src, dst)-sorted inside one (pp_rolling_fill); ``cnt`` from :func:`rolling_count` over the same windows and ``total`` its sum.
+    ``out = (index [2, T], weight [T], offset)``: the edges go to columns ``offset .. offset + total - 1`` of these buffers, and the first two
+    results are views of them."""
+    dev = require_device(keys, perm, lo, hi, cnt)
+    m, W, total = keys.numel(), lo.numel(), int(total)
+    if total >= _INT32_ROWS:
+        raise HipError(f"pp_rolling_fill: {total} edges in one group (2^31 - 16 or more)")
+    L = lib()
+    with torch.cuda.device(dev):
+        if out is None:
+            index, weight, offset = torch.empty((2, total), dtype=torch.int64, device=dev), torch.empty(total, dtype=torch.float32, device=dev), 0
+        else:
+            index, weight, offset = out
+            if index.dtype != torch.int64 or weight.dtype != torch.float32 or not index.is_contiguous() or not weight.is_contiguous() \
+                    or index.dim() != 2 or index.size(0) != 2 or weight.numel() != index.size(1) or offset < 0 or offset + total > index.size(1):
+                raise ValueError("rolling_fill: out must be a contiguous (int64 [2, T], float32 [T], offset) with room for the group")
+        nn = torch.empty(w1 - w0, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pp_rolling_fill_ws_bytes(m, total), dev)
+        src, dst = index[0, offset:], index[1, offset:]
+        check(L.pp_rolling_fill(_p(keys), keys.element_size(), _p(perm), m, int(num_nodes), _p(lo), _p(hi), W, int(w0), int(w1), _p(cnt), total,
+                                src.data_ptr(), dst.data_ptr(), weight[offset:].data_ptr(), _p(nn), _p(ws), ws.numel(), _stream()),
+              "pp_rolling_fill")
+    return index[:, offset:offset + total], weight[offset:offset + total], nn
