@@ -828,6 +828,37 @@ int pp_temporal_betweenness(const int64_t* edge_index, int64_t m, int64_t n, con
                             const int64_t* by_src_ptr, const int64_t* by_src, const int64_t* by_dst_ptr, const int64_t* by_dst,
                             double* partial, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ static shortest paths and centralities (pp_graph_paths.hip) */
+/* Unit-weight shortest paths from a list of source nodes on a static graph's source-major CSR (row_ptr [n+1] / col [m] int64, as
+ * Graph.row_ptr / Graph.col hold them; n, m < 2^31, PP_ERR_TOO_LARGE from 2^31 on): what shortest_paths_dijkstra / diameter / avg_path_length,
+ * src/pathpyG/algorithms/shortest_paths.py:13-52, get from scipy's Dijkstra with unweighted=True, and the distance totals behind
+ * closeness_centrality, src/pathpyG/algorithms/centrality.py:327-356 (networkx: incoming distances).  One workgroup per source at a time,
+ * level-synchronous frontier search; every stored edge counts once (parallel edges and self-loops are legal).  sources [n_sources] int64 node
+ * indices in [0, n), repeats allowed (a source outside the range is skipped).  Every output may be NULL (reach_in and dist_in only together):
+ *   dist [n_sources, n] int32: -1 = unreachable, 0 on the source itself;
+ *   pred [n_sources, n] int32: predecessor on a shortest path, the LARGEST node index among the tight ones; -9999 (scipy) on the source
+ *     itself and for unreachable nodes;
+ *   reach_in [n] / dist_in [n] int64, ADDED to: number of sources s != v that reach v / sum of their distances;
+ *   totals [3] int64, ADDED to (zero them first): sum of all finite distances to nodes other than the source, the largest finite distance,
+ *     number of (source, node != source) pairs without a path.  Integer atomics only: independent of order.
+ * ws: pp_graph_bfs_ws_bytes(n, n_sources), O(n) per workgroup, pp_graph_bfs_parts(n, n_sources) workgroups. */
+int64_t pp_graph_bfs_parts(int64_t n, int64_t n_sources);
+size_t pp_graph_bfs_ws_bytes(int64_t n, int64_t n_sources);
+int pp_graph_bfs(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t m, const int64_t* sources, int64_t n_sources, int32_t* dist,
+                 int32_t* pred, int64_t* reach_in, int64_t* dist_in, int64_t* totals, void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* Betweenness centrality as the reference computes it (betweenness_centrality, src/pathpyG/algorithms/centrality.py:83-134: Brandes with
+ * Python dicts per source), level-synchronous on the same CSR and source list (a repeated source counts twice, as in the loop of :105).
+ * A source's contribution to node w is npred[w] * delta[w], npred the number of stored edges into w from the previous level: the
+ * reference adds delta[w] once per entry of P[w] (:130-133).  partial [pp_graph_betweenness_parts(n, n_sources), n] float64: one row per
+ * workgroup, the centrality of node v is the sum of column v over the rows (summed by the caller in row order: bit-reproducible; no
+ * floating-point atomics in the dependencies).  reached [n] int32, zeroed by the caller: set to 1 for every node that some source reached
+ * at distance >= 1 — the keys of the reference's result.  ws: pp_graph_betweenness_ws_bytes(n, n_sources). */
+int64_t pp_graph_betweenness_parts(int64_t n, int64_t n_sources);
+size_t pp_graph_betweenness_ws_bytes(int64_t n, int64_t n_sources);
+int pp_graph_betweenness(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t m, const int64_t* sources, int64_t n_sources,
+                         double* partial, int32_t* reached, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 /* ------------------------------------------------------------------ order selection (pp_selection.hip) */
 
 /* Index arrays below are int32 (`*_wide` = 0) or int64 (1): the level-by-level builders keep int32 CSR arrays, Graph.row_ptr is int64.

@@ -60,6 +60,36 @@ def temporal_betweenness(edge_index, time, num_nodes: int, delta):
     return _hip.temporal_betweenness(ei, num_nodes, event_graph)
 
 
+def _graph_sources(graph, sources, dev):
+    """CSR of a Graph (wherever it lives) and the source indices (default: every node), on the compute device."""
+    n = graph.n
+    row_ptr, col = _stage(dev, graph.row_ptr, graph.col)
+    src = torch.arange(n, dtype=torch.int64, device=dev) if sources is None else torch.as_tensor(sources, dtype=torch.int64).reshape(-1).to(dev)
+    return row_ptr, col, n, src
+
+
+def graph_shortest_paths(graph, sources=None):
+    """``(dist, pred)`` int32 ``[len(sources), n]`` on the compute device (the dense route)."""
+    dev = compute_device(graph.data.edge_index)
+    return _hip.graph_bfs_dense(*_graph_sources(graph, sources, dev))
+
+
+def graph_path_totals(graph, sources=None):
+    """``(reach_in [n], dist_in [n], totals [3])`` as Python lists: one read-back, nothing of size n x n anywhere."""
+    dev = compute_device(graph.data.edge_index)
+    reach_in, dist_in, totals = _hip.graph_bfs_totals(*_graph_sources(graph, sources, dev))
+    n = graph.n
+    flat = torch.cat((reach_in, dist_in, totals)).tolist()
+    return flat[:n], flat[n:2 * n], flat[2 * n:]
+
+
+def graph_betweenness(graph, sources=None):
+    """``(bw float64 [n], reached bool [n])`` on the CPU."""
+    dev = compute_device(graph.data.edge_index)
+    bw, reached = _hip.graph_betweenness(*_graph_sources(graph, sources, dev))
+    return bw.cpu(), reached.cpu()
+
+
 def linegraph_lift(edge_index, num_nodes: int, edge_range=None):
     dev = compute_device(edge_index)
     (ei,) = _stage(dev, edge_index)

@@ -617,6 +617,68 @@ def temporal_betweenness(edge_index: torch.Tensor, num_nodes: int, event_graph: 
         return partial.sum(dim=0)
 
 
+# ------------------------------------------------------------------ static shortest paths (pp_graph_paths.hip)
+def _graph_csr(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, sources: torch.Tensor):
+    row_ptr, col, sources = (t.to(torch.int64).contiguous() for t in (row_ptr, col, sources))
+    dev = require_device(row_ptr, col, sources)
+    n, m = int(num_nodes), col.numel()
+    if row_ptr.numel() != n + 1:
+        raise ValueError(f"row_ptr must have num_nodes + 1 = {n + 1} entries, got {row_ptr.numel()}")
+    if sources.numel():
+        lo, hi = minmax(sources)
+        if lo < 0 or hi >= n:
+            raise IndexError(f"source node index out of range [0, {n})")
+    return row_ptr, col, sources, dev, n, m
+
+
+def graph_bfs_dense(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, sources: torch.Tensor):
+    """Unit-weight shortest paths from every entry of ``sources`` on a source-major CSR: ``(dist, pred)``, both int32
+    ``[len(sources), n]``; ``dist`` -1 = unreachable, ``pred`` the largest tight predecessor index, -9999 where there is none.
+    The only caller of ``pp_graph_bfs`` that allocates anything of size sources x n."""
+    row_ptr, col, sources, dev, n, m = _graph_csr(row_ptr, col, num_nodes, sources)
+    k = sources.numel()
+    L = lib()
+    with torch.cuda.device(dev):
+        dist = torch.empty((k, n), dtype=torch.int32, device=dev)
+        pred = torch.empty((k, n), dtype=torch.int32, device=dev)
+        ws = _workspace(L.pp_graph_bfs_ws_bytes(n, k), dev)
+        check(L.pp_graph_bfs(_p(row_ptr), _p(col), n, m, _p(sources), k, _p(dist), _p(pred), None, None, None, _p(ws), ws.numel(), _stream()),
+              "pp_graph_bfs")
+    return dist, pred
+
+
+def graph_bfs_totals(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, sources: torch.Tensor):
+    """The distance totals of the same searches without any per-pair output: ``(reach_in [n], dist_in [n], totals [3])`` int64 —
+    per node the number of sources (other than itself) that reach it and the sum of their distances; the sum of all finite
+    distances, the largest one and the number of (source, other node) pairs without a path.  O(n) memory per workgroup."""
+    row_ptr, col, sources, dev, n, m = _graph_csr(row_ptr, col, num_nodes, sources)
+    k = sources.numel()
+    L = lib()
+    with torch.cuda.device(dev):
+        acc = torch.zeros(2 * n + 3, dtype=torch.int64, device=dev)
+        reach_in, dist_in, totals = acc[:n], acc[n:2 * n], acc[2 * n:]
+        ws = _workspace(L.pp_graph_bfs_ws_bytes(n, k), dev)
+        check(L.pp_graph_bfs(_p(row_ptr), _p(col), n, m, _p(sources), k, None, None, _p(reach_in), _p(dist_in), _p(totals), _p(ws), ws.numel(),
+                             _stream()), "pp_graph_bfs")
+    return reach_in, dist_in, totals
+
+
+def graph_betweenness(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, sources: torch.Tensor):
+    """Betweenness in the reference's form from the given sources: ``(bw float64 [n], reached bool [n])``; ``reached`` marks the nodes
+    some source reached at distance >= 1.  The per-workgroup rows are summed in row order: the same bits on every run."""
+    row_ptr, col, sources, dev, n, m = _graph_csr(row_ptr, col, num_nodes, sources)
+    k = sources.numel()
+    L = lib()
+    with torch.cuda.device(dev):
+        parts = int(L.pp_graph_betweenness_parts(n, k))
+        partial = torch.zeros((parts, n), dtype=torch.float64, device=dev)
+        reached = torch.zeros(n, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pp_graph_betweenness_ws_bytes(n, k), dev)
+        check(L.pp_graph_betweenness(_p(row_ptr), _p(col), n, m, _p(sources), k, _p(partial), _p(reached), _p(ws), ws.numel(), _stream()),
+              "pp_graph_betweenness")
+        return partial.sum(dim=0), reached != 0
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""

@@ -1,4 +1,12 @@
-"""Algorithms on the hot path of pathpyG: order lifts and De Bruijn aggregation."""
+"""Algorithms on the hot path of pathpyG: order lifts, De Bruijn aggregation, shortest paths and centralities."""
+from . import centrality, shortest_paths  # noqa: F401
+from .centrality import (  # noqa: F401
+    betweenness_centrality,
+    closeness_centrality,
+    map_to_nodes,
+    path_node_traversals,
+    path_visitation_probabilities,
+)
 from .lift_order import (  # noqa: F401
     aggregate_edge_index,
     aggregate_node_attributes,
@@ -6,6 +14,7 @@ from .lift_order import (  # noqa: F401
     lift_order_edge_index_weighted,
 )
 from .rolling_time_window import RollingTimeWindow, RollingWindows, rolling_static_graphs  # noqa: F401
+from .shortest_paths import avg_path_length, diameter, shortest_paths_dijkstra  # noqa: F401
 from .temporal import (  # noqa: F401
     lift_order_temporal,
     temporal_betweenness_centrality,
