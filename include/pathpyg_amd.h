@@ -921,8 +921,8 @@ int pp_mon_zeroth_llh_f64(const int64_t* node_sequence, int64_t positions, const
  *   bit 2 when a pair has max_run events or more (max_run >= 1).
  * pp_rolling_fill, same windows, cnt as pp_rolling_count left it and total = the sum of cnt (< 2^31 - 16): the edges of the windows one
  *   window after the other, (src, dst)-sorted inside a window, to out_src / out_dst [total] int64 and out_weight [total] float32 (the
- *   number of the pair's events in the window); num_nodes_out [w1 - w0] int32 = 1 + the largest node index of the window, 0 for an empty
- *   one.  ws: pp_rolling_fill_ws_bytes(m, total). */
+ *   number of the pair's events in the window); num_nodes_out [w1 - w0] uint32 = 1 + the largest node index of the window (2^31 for node
+ *   2^31 - 1; num_nodes < 2^32), 0 for an empty one.  ws: pp_rolling_fill_ws_bytes(m, total). */
 int pp_rolling_key_bytes(int64_t num_nodes);
 size_t pp_rolling_group_ws_bytes(int64_t m, int64_t num_nodes);
 int pp_rolling_group(const int64_t* edge_index, const void* time, int time_dtype, int64_t m, int64_t num_nodes, void* keys_out,
@@ -934,7 +934,7 @@ int pp_rolling_count(const void* keys, int key_bytes, const uint32_t* perm, int6
 size_t pp_rolling_fill_ws_bytes(int64_t m, int64_t total);
 int pp_rolling_fill(const void* keys, int key_bytes, const uint32_t* perm, int64_t m, int64_t num_nodes, const int32_t* lo, const int32_t* hi,
                     int64_t W, int64_t w0, int64_t w1, const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight,
-                    int32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream);
+                    uint32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream);
 
 #ifdef __cplusplus
 }

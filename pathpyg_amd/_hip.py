@@ -2352,8 +2352,10 @@ def rolling_count(keys: torch.Tensor, perm: torch.Tensor, lo: torch.Tensor, hi: 
 
 def rolling_fill(keys: torch.Tensor, perm: torch.Tensor, num_nodes: int, lo: torch.Tensor, hi: torch.Tensor, w0: int, w1: int,
                  cnt: torch.Tensor, total: int, out: tuple | None = None):
-    """``(edge_index [2, total], edge_weight [total], num_nodes [w1 - w0] int32)`` of the windows ``w0 .. w1 - 1``, window after window and
+    """``(edge_index [2, total], edge_weight [total], num_nodes [w1 - w0])`` of the windows ``w0 .. w1 - 1``, window after window and
     (src, dst)-sorted inside one (pp_rolling_fill); ``cnt`` from :func:`rolling_count` over the same windows and ``total`` its sum.
+    ``num_nodes`` is an int32 tensor that holds UNSIGNED 32-bit words, as the keys do: a window with node 2^31 - 1 reads 2^31 through
+    ``.cpu().numpy().view(numpy.uint32)`` and -2^31 without the view.
     ``out = (index [2, T], weight [T], offset)``: the edges go to columns ``offset .. offset + total - 1`` of these buffers, and the first two
     results are views of them."""
     dev = require_device(keys, perm, lo, hi, cnt)

@@ -23,6 +23,12 @@ from ..data import Data, Lazy
 NATIVE = True                 # False: RollingTimeWindow always calls to_static_graph per window and rolling_static_graphs returns None
 BATCH_EDGES = 1 << 27         # edges of all windows of one fill-and-sort group (a single larger window is a group of its own)
 MAX_RUN = 1 << 24             # events of one node pair from which a float32 sum of ones and a converted count may differ
+# Largest number of windows a plan enumerates.  A plan spends host memory per window: the (start, end) tuple in `windows` (56 bytes), its
+# two Python numbers (24 to 32 bytes each) and its list slot (8); a slot each in `starts` and `ends` (16); lo and hi (8 together), the
+# report (4) and win_ptr (8) — about 160 bytes, 200 with the temporaries of the running sums.  2^22 windows are 0.8 GiB, so a plan
+# stays below 1 GiB.  Longer schedules, and an infinite last timestamp (which has no last window), go window by window, lazily, as in the
+# reference.  Must not exceed _hip._INT32_ROWS, the kernels' own limit.
+MAX_WINDOWS = 1 << 22
 
 _INT64 = (-(1 << 63), (1 << 63) - 1)
 
@@ -64,12 +70,19 @@ def eligible(g, window_size, step_size, weighted: bool = True) -> bool:
     return numbers and step_size > 0
 
 
-def schedule(start, end_time, window_size, step_size):
+def schedule(start, end_time, window_size, step_size, limit=None):
     """The reference's windows from ``start`` on (rolling_time_window.py:52-55): ``(t, t + window_size)`` while ``t <= end_time``, ``t``
     advanced by REPEATED addition of the step.  Returns ``(windows, next)`` with ``next`` the first start beyond ``end_time`` — or ``None``
-    when a step no longer changes ``t`` (a float step below the spacing of the times: the reference then yields one window for ever)."""
+    when a step no longer changes ``t`` (a float step below the spacing of the times: the reference then yields one window for ever), or
+    when there are more than ``limit`` windows: integer schedules are counted before the first one is made, float schedules (whose count
+    only the additions themselves give) stop at window ``limit + 1``."""
+    if limit is not None and _is_int(start) and _is_int(end_time) and _is_int(step_size) and step_size > 0 \
+            and start <= end_time and (end_time - start) // step_size + 1 > limit:
+        return None
     windows, t = [], start
     while t <= end_time:
+        if limit is not None and len(windows) >= limit:
+            return None
         windows.append((t, t + window_size))
         if t + step_size == t:
             return None
@@ -136,22 +149,22 @@ class _Plan(NamedTuple):
 
 
 def _plan(g, window_size, step_size, start_time=None, grouping=None):
-    """Windows, their event ranges and their edge counts — one read-back.  ``None``: the stream is not eligible."""
+    """Windows, their event ranges and their edge counts — one read-back.  ``None``: the stream is not eligible, or its schedule has more
+    than ``MAX_WINDOWS`` windows or no end (decided before any window is enumerated on integer times, at window ``MAX_WINDOWS + 1`` on
+    float times)."""
     if not eligible(g, window_size, step_size):
         return None
     time = g.data.time
     integer = time.dtype == torch.int64
     bounds = time[[0, -1]].tolist()
     start, end_time = (bounds[0] if start_time is None else start_time), bounds[1]
-    if not (_is_int(start) if integer else _is_number(start)) or end_time != end_time:
-        return None
-    planned = schedule(start, end_time, window_size, step_size)
+    if not (_is_int(start) if integer else _is_number(start)) or not (integer or math.isfinite(end_time)):
+        return None                 # (a NaN or infinite last timestamp: no schedule ends there)
+    planned = schedule(start, end_time, window_size, step_size, min(int(MAX_WINDOWS), _hip._INT32_ROWS - 1))
     if planned is None:
         return None
     windows, after = planned
     W = len(windows)
-    if W >= _hip._INT32_ROWS:
-        return None
     starts = [w[0] for w in windows] + [after]
     ends = [w[1] for w in windows]
     if W == 0:                      # the start lies beyond the last event already
@@ -193,15 +206,18 @@ def _build(plan: _Plan, w0: int, w1: int) -> RollingWindows:
             cnt, _ = _hip.rolling_count(keys, perm, plan.lo, plan.hi, a, b, MAX_RUN, flags)
         parts.append(_hip.rolling_fill(keys, perm, plan.g.data.num_nodes, plan.lo, plan.hi, a, b, cnt, int(ptr[b] - ptr[a]),
                                        out=(index, weight, int(ptr[a] - ptr[w0])))[2])
-    num_nodes = (parts[0] if len(parts) == 1 else torch.cat(parts)).tolist() if parts else []
+    # (the node counts are unsigned 32-bit words in an int32 tensor: node 2^31 - 1 makes a window of 2^31 nodes)
+    num_nodes = (parts[0] if len(parts) == 1 else torch.cat(parts)).cpu().numpy().view(np.uint32).tolist() if parts else []
     return RollingWindows(plan.windows[w0:w1], ptr[w0:w1 + 1] - ptr[w0], index, weight, num_nodes, plan.g.mapping)
 
 
 def rolling_static_graphs(g, window_size, step_size=1, start_time=None) -> RollingWindows | None:
     """The weighted static graphs of all windows ``[t, t + window_size)`` of the temporal graph ``g``, ``t`` running from ``start_time``
     (default ``g.start_time``) in steps of ``step_size`` while ``t <= g.end_time``, as one :class:`RollingWindows` batch.  ``None`` when the
-    stream is not eligible for the batched pass (:func:`eligible`, or what the device found: unsorted or NaN times, a node index outside
-    the graph, a node pair with ``MAX_RUN`` events or more) — iterate a :class:`RollingTimeWindow` then."""
+    stream is not eligible for the batched pass (:func:`eligible`; a schedule of more than ``MAX_WINDOWS`` windows, which is refused
+    before it is enumerated, or one that never ends: an infinite last timestamp, a step that does not advance; or what the device found:
+    unsorted or NaN times, a node index outside the graph, a node pair with ``MAX_RUN`` events or more) — iterate a
+    :class:`RollingTimeWindow` then, which goes window by window and lazily."""
     plan = _plan(g, window_size, step_size, start_time)
     if plan is None:
         return None

@@ -17,7 +17,8 @@
 //   pp_rolling_fill     scan of cnt, then every head (j, w) writes {w, j} in pair-major order (k_roll_fill), a stable radix sort on the
 //                       ceil(log2 W) bits of w makes that window-major with (src, dst) order inside a window — coalesce's order — and
 //                       k_roll_emit writes src, dst and the weight of every edge: the number of positions from j on, inside the run, whose
-//                       event is < hi[w] (perm ascends: a galloping bisection from j), as float32; num_nodes[w] = max node + 1.
+//                       event is < hi[w] (perm ascends: a galloping bisection from j), as float32; num_nodes[w] = max node + 1, an
+//                       unsigned 32-bit word: node 2^31 - 1 gives 2^31.
 // Windows may overlap (an event is head material in many) or leave gaps (cnt = 0); a range w0..w1 of windows restricts count and fill
 // to a group whose edges fit a budget.  lo / hi are read at random by every thread: they are staged in LDS while the group has at most
 // kRollLdsWindows windows and are left to the caches beyond that.
@@ -149,9 +150,10 @@ __global__ __launch_bounds__(kEmitBlock) void k_roll_emit(const KeyT* __restrict
                                                      const int32_t* __restrict__ hi, int w0, int wn, const uint32_t* __restrict__ wkey,
                                                      const uint32_t* __restrict__ pos, int64_t total, int64_t* __restrict__ out_src,
                                                      int64_t* __restrict__ out_dst, float* __restrict__ out_weight,
-                                                     int32_t* __restrict__ nn) {
+                                                     uint32_t* __restrict__ nn) {
     const int64_t q = (int64_t)blockIdx.x * kEmitBlock + threadIdx.x;
-    int wl = -1, top = 0;
+    int wl = -1;
+    uint32_t top = 0;            // (unsigned: the largest admitted node, 2^32 - 2, gives 2^32 - 1; an int would wrap from node 2^31 - 1 on)
     if (q < total) {
         const int64_t j = pos[q];
         const int w = (int)wkey[q];
@@ -173,21 +175,22 @@ __global__ __launch_bounds__(kEmitBlock) void k_roll_emit(const KeyT* __restrict
             out_src[q] = u;
             out_dst[q] = v;
             out_weight[q] = (float)(first - j);
-            top = (int)((u > v ? u : v) + 1);
+            top = (uint32_t)((u > v ? u : v) + 1);
         }
     }
     // num_nodes of the window.  Atomics of one address queue up (measured: about 7 ns each — a window of 10^5 edges kept the kernel waiting
     // for 1,500 of them), so the maxima are first merged per wave (its edges mostly belong to one window) and per workgroup in LDS (the
     // windows of kEmitBlock consecutive edges are the first one + 0 .. kEmitSpan - 1, or they go to memory directly): one atomic per
     // workgroup and window.
-    __shared__ int s_first, s_top[kEmitSpan];
+    __shared__ int s_first;
+    __shared__ uint32_t s_top[kEmitSpan];
     if (threadIdx.x == 0) s_first = wl;
     if (threadIdx.x < kEmitSpan) s_top[threadIdx.x] = 0;
     __syncthreads();
     const int first_w = s_first;
     const int ref = __builtin_amdgcn_readfirstlane(wl);
     const bool uniform = __all(wl == ref || wl < 0);
-    const int mine = uniform ? wave_max(wl < 0 ? 0 : top) : top;
+    const uint32_t mine = uniform ? wave_max(wl < 0 ? 0u : top) : top;
     if (wl >= 0 && (!uniform || lane_id() == 0)) {            // (uniform with a live lane: lane 0 is live and speaks for the wave)
         const int d = wl - first_w;
         if (first_w >= 0 && d >= 0 && d < kEmitSpan) atomicMax(&s_top[d], mine); else atomicMax(&nn[wl], mine);
@@ -252,10 +255,10 @@ static int rolling_count(const KeyT* keys, const uint32_t* perm, int64_t m, cons
 
 template <typename KeyT>
 static int rolling_fill(const KeyT* keys, const uint32_t* perm, int64_t m, int bits, const int32_t* lo, const int32_t* hi, int w0, int w1,
-                        const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight, int32_t* nn, void* ws,
+                        const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight, uint32_t* nn, void* ws,
                         hipStream_t st) {
     const int wn = w1 - w0;
-    PP_HIP(hipMemsetAsync(nn, 0, (size_t)wn * sizeof(int32_t), st));
+    PP_HIP(hipMemsetAsync(nn, 0, (size_t)wn * sizeof(uint32_t), st));
     if (total == 0) return PP_OK;
     RollFillWs w = carve_roll_fill(ws, m, total);
     int rc = exclusive_scan<int32_t, int32_t>(cnt, m, w.ptr, true, nullptr, w.scan, w.scan_bytes, st);
@@ -351,9 +354,11 @@ size_t pp_rolling_fill_ws_bytes(int64_t m, int64_t total) { return carve_roll_fi
 
 int pp_rolling_fill(const void* keys, int key_bytes, const uint32_t* perm, int64_t m, int64_t num_nodes, const int32_t* lo, const int32_t* hi,
                     int64_t W, int64_t w0, int64_t w1, const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight,
-                    int32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream) {
+                    uint32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     PP_ROLL_RANGE("pp_rolling_fill");
+    PP_REQUIRE(num_nodes >= 0 && num_nodes < ((int64_t)1 << 32), PP_ERR_ARG, "pp_rolling_fill: num_nodes=%lld outside [0, 2^32): a window's node count is 32 bits",
+               (long long)num_nodes);
     PP_REQUIRE(key_bytes == pp_rolling_key_bytes(num_nodes), PP_ERR_ARG, "pp_rolling_fill: key width does not fit num_nodes");
     PP_REQUIRE(total >= 0 && total < (int64_t)0x7ffffff0, PP_ERR_TOO_LARGE, "pp_rolling_fill: total=%lld outside [0, 2^31 - 16)", (long long)total);
     PP_REQUIRE(m > 0 || total == 0, PP_ERR_ARG, "pp_rolling_fill: edges without events");

@@ -84,7 +84,7 @@ def rolling_fill(keys, perm, num_nodes, lo, hi, w0, w1, cnt, total, out=None):
         index, weight, offset = torch.empty((2, total), dtype=torch.int64), torch.empty(total, dtype=torch.float32), 0
     else:
         index, weight, offset = out
-    nn = np.zeros(wn, dtype=np.int32)
+    nn = np.zeros(wn, dtype=np.uint32)                                   # unsigned, as in the kernel: node 2^31 - 1 makes 2^31
     for q in range(total):                                               # k_roll_emit
         j, w = pos[q], wkey[q]
         key, end = int(k[j]), hi_[w0 + w]
@@ -93,8 +93,8 @@ def rolling_fill(keys, perm, num_nodes, lo, hi, w0, w1, cnt, total, out=None):
             stop += 1
         u, v = key >> bits, key & ((1 << bits) - 1)
         index[0, offset + q], index[1, offset + q], weight[offset + q] = int(u), int(v), float(stop - j)
-        nn[w] = max(nn[w], max(u, v) + 1)
-    return index[:, offset:offset + total], weight[offset:offset + total], torch.from_numpy(nn)
+        nn[w] = max(int(nn[w]), max(u, v) + 1)
+    return index[:, offset:offset + total], weight[offset:offset + total], torch.from_numpy(nn.view(np.int32))       # (the wrapper's int32 tensor)
 
 
 def install(monkeypatch):
