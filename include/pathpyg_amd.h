@@ -859,6 +859,44 @@ size_t pp_graph_betweenness_ws_bytes(int64_t n, int64_t n_sources);
 int pp_graph_betweenness(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t m, const int64_t* sources, int64_t n_sources,
                          double* partial, int32_t* reached, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ connected components (pp_graph_components.hip) */
+/* Weakly or strongly connected components of a static graph: what connected_components / largest_connected_component,
+ * src/pathpyG/algorithms/components.py:14-53, get from scipy.sparse.csgraph.connected_components on a host copy and from a Python loop over
+ * graph.edges.  edge_index [2, m] int64 row-major (any order); n, m < 2^31, PP_ERR_TOO_LARGE from 2^31 on, before anything is launched.
+ * Every stored edge counts; parallel edges and self-loops are legal and change nothing; an endpoint outside [0, n) is skipped, never
+ * dereferenced.  n == 0 and m == 0 are legal.
+ *   strong == 0: lock-free union-find over the edge list (path halving, atomicCAS hooking of the larger root under the smaller, after every
+ *     node was hooked to its smallest smaller neighbour); the four CSR / CSC pointers are not read and may be NULL.
+ *   strong != 0: forward colouring + backward search with trimming on the CSR (row_ptr [n+1], col [m]: out-edges) and the CSC (col_ptr [n+1],
+ *     row [m]: in-edges) as Graph holds them; self-loops are ignored; edge_index is not read.  The number of sweeps grows with the longest
+ *     shortest path (a directed ring of k nodes: about 2k launches).
+ * labels [n] int32: components are numbered in the order of their SMALLEST node index (weak: scipy's numbering; strong: scipy's partition,
+ * numbered this way instead of in Tarjan's completion order).  sizes [n] int64: the first *count entries are the component sizes, the rest
+ * is zero.  count [1] int64.  labels, sizes and count are DEVICE pointers.  stats [4] is a HOST array or NULL: rounds, trim sweeps, colour
+ * sweeps, backward sweeps (all 0 for strong == 0).  Integer atomics only: every output is the same on every run.
+ * Fixpoints are host loops over launches with a device word read back in between (the call synchronises the stream when strong != 0); each is
+ * bounded by n + 1 sweeps and the rounds by n: PP_ERR_HIP when a bound is hit.  ws: pp_graph_components_ws_bytes(n, m, strong). */
+size_t pp_graph_components_ws_bytes(int64_t n, int64_t m, int strong);
+int pp_graph_components(const int64_t* edge_index, int64_t m, int64_t n, const int64_t* row_ptr, const int64_t* col, const int64_t* col_ptr,
+                        const int64_t* row, int strong, int32_t* labels, int64_t* sizes, int64_t* count, int64_t* stats, void* ws,
+                        size_t ws_bytes, pp_stream_t stream);
+
+/* out2 [2] int64 (device) = {label, size} of the largest of the first count[0] entries of sizes; among equal sizes the smallest label: the
+ * choice of Counter(labels).most_common(1) under the numbering above (components.py:46-47).  {-1, 0} when count[0] == 0. */
+int pp_graph_components_largest(const int64_t* sizes, const int64_t* count, int64_t* out2, pp_stream_t stream);
+
+/* The sub-graph of one component, compacted in stored order with the scan of pp_scan.hip:
+ * pp_graph_component_nodes: nodes_out [nodes_cap] int64 = the node indices v with labels[v] == keep, ascending (those beyond nodes_cap are
+ *   not written); count_out [1] (device) their number.
+ * pp_graph_component_edges: the stored edges whose two ends both carry the label `keep`, in stored order, renumbered through
+ *   new_index [n] int64 (read only at kept nodes): edges_out [2, m] int64 with row stride m, the first count_out[0] columns of each row valid.
+ * ws: pp_graph_component_keep_ws_bytes(n) / (m). */
+size_t pp_graph_component_keep_ws_bytes(int64_t count);
+int pp_graph_component_nodes(const int32_t* labels, int64_t n, int64_t keep, int64_t* nodes_out, int64_t nodes_cap, int64_t* count_out, void* ws,
+                             size_t ws_bytes, pp_stream_t stream);
+int pp_graph_component_edges(const int64_t* edge_index, int64_t m, int64_t n, const int32_t* labels, int64_t keep, const int64_t* new_index,
+                             int64_t* edges_out, int64_t* count_out, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 /* ------------------------------------------------------------------ order selection (pp_selection.hip) */
 
 /* Index arrays below are int32 (`*_wide` = 0) or int64 (1): the level-by-level builders keep int32 CSR arrays, Graph.row_ptr is int64.

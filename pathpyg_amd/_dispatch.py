@@ -90,6 +90,17 @@ def graph_betweenness(graph, sources=None):
     return bw.cpu(), reached.cpu()
 
 
+def graph_components(graph, strong: bool, with_stats: bool = False):
+    """``(count int64 [1], labels int32 [n], sizes int64 [n])`` on the compute device (csrc/pp_graph_components.hip); with ``with_stats`` also
+    the host list ``[rounds, trim sweeps, colour sweeps, backward sweeps]``.  A CPU-resident graph is staged."""
+    dev = compute_device(graph.data.edge_index)
+    (ei,) = _stage(dev, graph.data.edge_index)
+    csr = _stage(dev, graph.row_ptr, graph.col) if strong else None
+    csc = _stage(dev, graph.col_ptr, graph.row) if strong else None
+    count, labels, sizes, stats = _hip.graph_components(ei, graph.n, csr, csc)
+    return (count, labels, sizes, stats) if with_stats else (count, labels, sizes)
+
+
 def linegraph_lift(edge_index, num_nodes: int, edge_range=None):
     dev = compute_device(edge_index)
     (ei,) = _stage(dev, edge_index)

@@ -679,6 +679,85 @@ def graph_betweenness(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, 
         return partial.sum(dim=0), reached != 0
 
 
+# ------------------------------------------------------------------ connected components (pp_graph_components.hip)
+def _graph_both(edge_index: torch.Tensor, num_nodes: int, csr, csc):
+    ei = _edge_index(edge_index)
+    n, m = int(num_nodes), ei.size(1)
+    parts = [None, None, None, None]
+    if csr is not None:
+        parts = [t.to(torch.int64).contiguous() for t in (*csr, *csc)]
+        for ptr, idx, name in ((parts[0], parts[1], "row_ptr / col"), (parts[2], parts[3], "col_ptr / row")):
+            if ptr.numel() != n + 1 or idx.numel() != m:
+                raise ValueError(f"{name} must have num_nodes + 1 = {n + 1} and {m} entries, got {ptr.numel()} and {idx.numel()}")
+    dev = require_device(ei, *parts)
+    return ei, parts, dev, n, m
+
+
+def graph_components(edge_index: torch.Tensor, num_nodes: int, csr=None, csc=None):
+    """Connected components of the stored edges: weak from the edge list alone; strong when ``csr = (row_ptr, col)`` and
+    ``csc = (col_ptr, row)`` are given.  Returns ``(count int64 [1], labels int32 [n], sizes int64 [n], stats)``, all tensors on the
+    device: labels numbered by each component's smallest node index, the first ``count`` entries of ``sizes`` valid; ``stats`` is the
+    host list ``[rounds, trim sweeps, colour sweeps, backward sweeps]``."""
+    strong = csr is not None
+    if strong != (csc is not None):
+        raise ValueError("graph_components: the CSR and the CSC come together")
+    ei, (row_ptr, col, col_ptr, row), dev, n, m = _graph_both(edge_index, num_nodes, csr, csc)
+    L = lib()
+    with torch.cuda.device(dev):
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        acc = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        sizes, count = acc[:n], acc[n:]
+        stats = (ctypes.c_int64 * 4)()
+        ws = _workspace(L.pp_graph_components_ws_bytes(n, m, int(strong)), dev)
+        check(L.pp_graph_components(_p(ei), m, n, _p(row_ptr), _p(col), _p(col_ptr), _p(row), int(strong), _p(labels), _p(sizes), _p(count),
+                                    ctypes.addressof(stats), _p(ws), ws.numel(), _stream()), "pp_graph_components")
+    return count, labels, sizes, list(stats)
+
+
+def graph_components_largest(sizes: torch.Tensor, count: torch.Tensor) -> tuple[int, int]:
+    """``(label, size)`` of the largest component, the smallest label among equals (one 16-byte read-back); ``(-1, 0)`` without components."""
+    dev = require_device(sizes, count)
+    with torch.cuda.device(dev):
+        out = torch.empty(2, dtype=torch.int64, device=dev)
+        check(lib().pp_graph_components_largest(_p(sizes), _p(count), _p(out), _stream()), "pp_graph_components_largest")
+        label, size = out.tolist()
+    return label, size
+
+
+def graph_component_nodes(labels: torch.Tensor, keep: int, size: int) -> torch.Tensor:
+    """The ``size`` node indices that carry the label ``keep``, ascending (int64, on the device)."""
+    labels = labels.contiguous()
+    dev = require_device(labels)
+    n = labels.numel()
+    L = lib()
+    with torch.cuda.device(dev):
+        nodes = torch.empty(int(size), dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_graph_component_keep_ws_bytes(n), dev)
+        check(L.pp_graph_component_nodes(_p(labels), n, int(keep), _p(nodes), nodes.numel(), _p(count), _p(ws), ws.numel(), _stream()),
+              "pp_graph_component_nodes")
+    return nodes
+
+
+def graph_component_edges(edge_index: torch.Tensor, labels: torch.Tensor, keep: int, new_index: torch.Tensor) -> torch.Tensor:
+    """The stored edges with both ends labelled ``keep``, in stored order, renumbered through ``new_index`` [n]: int64 ``[2, kept]``."""
+    ei = _edge_index(edge_index)
+    labels, new_index = labels.contiguous(), new_index.to(torch.int64).contiguous()
+    dev = require_device(ei, labels, new_index)
+    n, m = labels.numel(), ei.size(1)
+    if new_index.numel() != n:
+        raise ValueError(f"new_index must have {n} entries, got {new_index.numel()}")
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty((2, m), dtype=torch.int64, device=dev)
+        count = torch.empty(1, dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_graph_component_keep_ws_bytes(m), dev)
+        check(L.pp_graph_component_edges(_p(ei), m, n, _p(labels), int(keep), _p(new_index), _p(out), _p(count), _p(ws), ws.numel(), _stream()),
+              "pp_graph_component_edges")
+        kept = int(count.item())
+        return out[:, :kept].contiguous()
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""

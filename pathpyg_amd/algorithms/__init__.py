@@ -1,5 +1,6 @@
 """Algorithms on the hot path of pathpyG: order lifts, De Bruijn aggregation, shortest paths and centralities."""
-from . import centrality, shortest_paths  # noqa: F401
+from . import centrality, components, shortest_paths  # noqa: F401
+from .components import connected_components, largest_connected_component  # noqa: F401
 from .centrality import (  # noqa: F401
     betweenness_centrality,
     closeness_centrality,
