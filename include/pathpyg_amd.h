@@ -821,7 +821,9 @@ int pp_temporal_bfs(const int64_t* edge_index, int64_t m, int64_t n, const int64
 /* Temporal betweenness centrality (temporal_betweenness_centrality, src/pathpyG/algorithms/centrality.py:164-297: Brandes on the event
  * DAG) in level-synchronous form, one workgroup per source node.  Inputs as pp_temporal_bfs plus the events grouped by their head
  * node (by_dst_ptr [n+1] / by_dst [m]).  partial [pp_temporal_betweenness_parts(m,n), n] float64: one row per workgroup; the
- * centrality of node v is the sum of column v over the rows (summed by the caller in row order: bit-reproducible). */
+ * centrality of node v is the sum of column v over the rows (summed by the caller in row order: bit-reproducible while every path count
+ * stays below 2^53, where the float64 counts are exact; within summation rounding up to 2^1024; from there on a count is inf, as the
+ * reference's float counts are, and a ratio inf / inf counts as 0.0, the reference's isnan guard, centrality.py:282-289). */
 int64_t pp_temporal_betweenness_parts(int64_t m, int64_t n);
 size_t pp_temporal_betweenness_ws_bytes(int64_t m, int64_t n);
 int pp_temporal_betweenness(const int64_t* edge_index, int64_t m, int64_t n, const int64_t* succ_ptr, const int64_t* succ,
@@ -852,8 +854,11 @@ int pp_graph_bfs(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t 
  * A source's contribution to node w is npred[w] * delta[w], npred the number of stored edges into w from the previous level: the
  * reference adds delta[w] once per entry of P[w] (:130-133).  partial [pp_graph_betweenness_parts(n, n_sources), n] float64: one row per
  * workgroup, the centrality of node v is the sum of column v over the rows (summed by the caller in row order: bit-reproducible; no
- * floating-point atomics in the dependencies).  reached [n] int32, zeroed by the caller: set to 1 for every node that some source reached
- * at distance >= 1 — the keys of the reference's result.  ws: pp_graph_betweenness_ws_bytes(n, n_sources). */
+ * floating-point atomics in the dependencies).  reached [n] int32, zeroed by the caller, two bits per node: bit 0 is set for every node
+ * that some source reached at distance >= 1 — the keys of the reference's result; bit 1 is set for every node to which some searched source
+ * has 2^1024 or more shortest paths.  Path counts are float64 where the reference's are unbounded ints: exact (and the result
+ * bit-reproducible) below 2^53, within summation rounding up to 2^1024, inf from there on — if any bit 1 is set, `partial` holds nothing of
+ * use and the caller has to refuse the call.  ws: pp_graph_betweenness_ws_bytes(n, n_sources). */
 int64_t pp_graph_betweenness_parts(int64_t n, int64_t n_sources);
 size_t pp_graph_betweenness_ws_bytes(int64_t n, int64_t n_sources);
 int pp_graph_betweenness(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t m, const int64_t* sources, int64_t n_sources,

@@ -198,10 +198,15 @@ def temporal_betweenness_levels(edge_index: torch.Tensor, time: torch.Tensor, nu
                 for w in succ[ptr[v]:ptr[v + 1]]:
                     if level[w] == d + 1:
                         x = sigma[v] / sigma[w]
+                        if x != x:                                           # inf / inf at 2**1024 paths: the reference's isnan guard
+                            x = 0.0
                         acc += x * dep[w]
                         cr += dep[w] * x
                 if level[v] == dist_fo[dst[v]]:
-                    acc += sigma[v] / sigma_fo[dst[v]]
+                    x = sigma[v] / sigma_fo[dst[v]]
+                    if x != x:
+                        x = 0.0
+                    acc += x
                 dep[v] = acc
                 credit[v] = cr
         row = np.zeros(n)

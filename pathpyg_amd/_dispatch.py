@@ -84,10 +84,16 @@ def graph_path_totals(graph, sources=None):
 
 
 def graph_betweenness(graph, sources=None):
-    """``(bw float64 [n], reached bool [n])`` on the CPU."""
+    """``(bw float64 [n], reached bool [n])`` on the CPU.  ``OverflowError`` if a searched source has 2**1024 or more shortest paths to
+    some node: float64 path counts end there, and nothing computed from an infinite count is returned."""
     dev = compute_device(graph.data.edge_index)
-    bw, reached = _hip.graph_betweenness(*_graph_sources(graph, sources, dev))
-    return bw.cpu(), reached.cpu()
+    bw, reached, overflow = _hip.graph_betweenness(*_graph_sources(graph, sources, dev))
+    bw, reached, overflow = bw.cpu(), reached.cpu(), overflow.cpu()
+    if bool(overflow.any()):
+        v = int(overflow.nonzero()[0])
+        raise OverflowError(f"betweenness_centrality: node index {v} has 2**1024 or more shortest paths from a source; path counts are "
+                            "float64 and end there (the reference counts in unbounded Python ints)")
+    return bw, reached
 
 
 def graph_components(graph, strong: bool, with_stats: bool = False):

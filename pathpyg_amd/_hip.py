@@ -664,8 +664,10 @@ def graph_bfs_totals(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, s
 
 
 def graph_betweenness(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, sources: torch.Tensor):
-    """Betweenness in the reference's form from the given sources: ``(bw float64 [n], reached bool [n])``; ``reached`` marks the nodes
-    some source reached at distance >= 1.  The per-workgroup rows are summed in row order: the same bits on every run."""
+    """Betweenness in the reference's form from the given sources: ``(bw float64 [n], reached bool [n], overflow bool [n])``; ``reached``
+    marks the nodes some source reached at distance >= 1, ``overflow`` those to which some searched source has 2**1024 or more shortest
+    paths — if any is set, ``bw`` is meaningless.  The per-workgroup rows are summed in row order: the same bits on every run while the
+    path counts stay below 2**53."""
     row_ptr, col, sources, dev, n, m = _graph_csr(row_ptr, col, num_nodes, sources)
     k = sources.numel()
     L = lib()
@@ -676,7 +678,7 @@ def graph_betweenness(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, 
         ws = _workspace(L.pp_graph_betweenness_ws_bytes(n, k), dev)
         check(L.pp_graph_betweenness(_p(row_ptr), _p(col), n, m, _p(sources), k, _p(partial), _p(reached), _p(ws), ws.numel(), _stream()),
               "pp_graph_betweenness")
-        return partial.sum(dim=0), reached != 0
+        return partial.sum(dim=0), (reached & 1) != 0, (reached & 2) != 0
 
 
 # ------------------------------------------------------------------ connected components (pp_graph_components.hip)

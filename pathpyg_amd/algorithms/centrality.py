@@ -71,9 +71,13 @@ def betweenness_centrality(graph, sources: list | None = None) -> dict:
     accumulation, which adds ``delta[w]`` once per predecessor EDGE of ``w`` (its statement sits inside the loop over ``P[w]``):
     a source contributes ``npred[w] * delta[w]``.  networkx's unnormalised betweenness is a different number on most graphs.
 
-    Every source's search runs on the GPU, level-synchronous: path counts ``sigma`` are integer-valued float64 (exact below 2**53,
-    where the reference's Python ints are unbounded), dependencies are pulled in CSR order without floating-point atomics, so the
-    result is the same on every run and equals the reference up to float64 summation order.  O(n m) work for all sources.
+    Every source's search runs on the GPU, level-synchronous: path counts ``sigma`` are integer-valued float64 where the reference's
+    Python ints are unbounded, and dependencies are pulled in CSR order without floating-point atomics.  While every count of a
+    searched source stays below 2**53 the counts are exact, the result has the same bits on every run and equals the reference up to
+    float64 summation order.  Between 2**53 and 2**1024 the counts round as they are added, in an order that may differ from run to
+    run: the result stays within summation rounding of the reference, its last bits are not reproducible.  A count of 2**1024 or
+    more does not fit a float64: the call raises ``OverflowError`` if some node has that many shortest paths from one of the searched
+    sources (other sources of the same graph are served).  O(n m) work for all sources.
     """
     bw = defaultdict(lambda: 0.0)
     idx = source_indices(graph, sources)

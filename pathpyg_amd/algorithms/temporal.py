@@ -63,8 +63,12 @@ def temporal_betweenness_centrality(graph, delta: int = 1):
     src/pathpyG/algorithms/centrality.py:164-297: Brandes' algorithm on the event DAG, pure-Python dict/deque loops per source).
 
     Here every source node runs the level-synchronous form of the same recurrences on the GPU (``pp_temporal_betweenness``):
-    identical path counts, dependencies accumulated in float64 — equal to the reference up to summation order (its known answer
-    is reproduced exactly).  Returns a ``defaultdict`` node id -> centrality with an entry for every node."""
+    float64 path counts like the reference's, dependencies accumulated in float64 — equal to the reference up to summation order
+    (its known answer is reproduced exactly).  While every path count stays below 2**53 the counts are exact and the result has the
+    same bits on every run; between 2**53 and 2**1024 the counts round as they are added, in an order that may differ from run to
+    run, and the result stays within summation rounding of the reference; from 2**1024 on a count is ``inf`` here as it is there, and
+    the backward pass follows the reference's guard (centrality.py:282-289): a ratio ``inf / inf`` counts as 0.0, so the result is
+    finite wherever the reference's is.  Returns a ``defaultdict`` node id -> centrality with an entry for every node."""
     from collections import defaultdict
 
     data = graph.data

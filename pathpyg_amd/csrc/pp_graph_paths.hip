@@ -109,7 +109,10 @@ __global__ __launch_bounds__(kBlock) void k_graph_bfs(const int64_t* __restrict_
 // ---------------------------------------------------------------------------------------------------------------------
 // Brandes' betweenness in the reference's own form (centrality.py:83-134), level-synchronous:
 //   forward : BFS levels; sigma[w] += sigma[v] and npred[w] += 1 for every stored edge (v, w) from the previous level (centrality.py:119-126;
-//             integer-valued doubles: the atomic adds are exact in any order below 2^53);
+//             integer-valued doubles: below 2^53 the atomic adds are exact in any order and the result has the same bits on every run;
+//             from 2^53 to 2^1024 they round, in an order that may differ from run to run, and the result is within summation rounding of
+//             the reference's unbounded ints; a count of 2^1024 or more is inf and cannot be matched in float64 at all (inf / inf, x / inf):
+//             the search ORs 2 into reached[v] of such a node v and the caller refuses the call — per searched source, not per graph);
 //   backward: deepest level first; dep[v] = sum over v's out-edges to the next level of sigma[v] / sigma[w] * (1 + dep[w]) in CSR order
 //             (a hub: lane j sums the entries j, j + 64, ... and the 64 partial sums meet in a fixed butterfly) — no floating-point atomics;
 //   credit  : bw[w] += npred[w] * dep[w]: the reference adds delta[w] to bw[w] INSIDE its loop over P[w] (centrality.py:130-133), once per
@@ -162,7 +165,12 @@ __global__ __launch_bounds__(kBlock) void k_graph_betweenness(const int64_t* __r
             __syncthreads();
             if (begin == end) break;
             if (threadIdx.x == 0) w.level_start[depth + 1] = end;
-            expand_frontier(row_ptr, col, w.order, begin, end, [&](int32_t v) { return w.sigma[v]; }, [&](int32_t, double sv, int64_t x) {
+            auto count_of = [&](int32_t v) {                                             // every reached node is a frontier entry exactly once
+                const double sv = w.sigma[v];
+                if (sv > __DBL_MAX__) atomicOr(&reached[v], 2);                          // 2^1024 or more shortest paths: the caller refuses
+                return sv;
+            };
+            expand_frontier(row_ptr, col, w.order, begin, end, count_of, [&](int32_t, double sv, int64_t x) {
                 if ((uint64_t)x >= (uint64_t)n) return;
                 const int32_t old = atomicCAS(&w.level[x], -1, depth + 1);
                 if (old == -1) w.order[atomicAdd(&s_tail, 1)] = (int32_t)x;
@@ -182,7 +190,7 @@ __global__ __launch_bounds__(kBlock) void k_graph_betweenness(const int64_t* __r
             auto finish = [&](int32_t v, double acc) {
                 w.dep[v] = acc;
                 bw[v] += (double)w.npred[v] * acc;
-                reached[v] = 1;                                                          // every writer stores the same value
+                if (!(reached[v] & 1)) atomicOr(&reached[v], 1);                         // (an OR: bit 1 of another search's refusal survives)
             };
             for (int64_t base = (int64_t)lo + wave_id() * kWave; base < hi; base += kBlock) {
                 const int64_t k = base + lane_id();

@@ -76,7 +76,10 @@ __global__ __launch_bounds__(kBlock) void k_temporal_bfs(const int64_t* __restri
 // Brandes' algorithm on the event DAG with a virtual source per first-order node, pure-Python dict/deque loops).
 // Level-synchronous form, one workgroup per source node:
 //   forward : BFS levels over the events; sigma[e] = number of shortest event paths from the source (integer-valued doubles:
-//             the atomic adds are exact in any order); dist_fo / sigma_fo per first-order node from the TIGHT events into it;
+//             below 2^53 the atomic adds are exact in any order and the result has the same bits on every run; from 2^53 to 2^1024
+//             they round, in an order that may differ from run to run: the result is within summation rounding of the reference;
+//             from 2^1024 on a count is inf, as in the reference's float counts, and the backward pass takes the reference's guard:
+//             a ratio inf / inf counts as 0.0); dist_fo / sigma_fo per first-order node from the TIGHT events into it;
 //   backward: levels in reverse; every event pulls x * dep[w] from its successors on the next level (x = sigma[v] / sigma[w]) in
 //             CSR order, adds its own target term, and is credited dep[w] * x towards its head node;
 //   per node: credits summed over the node's in-events in event order (no floating-point atomics anywhere);
@@ -179,13 +182,18 @@ __global__ __launch_bounds__(kBlock) void k_temporal_betweenness(const int64_t* 
                 for (int64_t p = succ_ptr[v]; p < succ_ptr[v + 1]; ++p) {
                     const int32_t f = (int32_t)succ[p];
                     if (w.level[f] == d + 1) {
-                        const double x = sv / w.sigma[f];
+                        double x = sv / w.sigma[f];
+                        if (x != x) x = 0.0;                                               // inf / inf: centrality.py:287-289
                         acc += x * w.dep[f];
                         cr += w.dep[f] * x;
                     }
                 }
                 const int64_t head = dst[v];
-                if (w.dist_fo[head] == d) acc += sv / w.sigma_fo[head];
+                if (w.dist_fo[head] == d) {
+                    double x = sv / w.sigma_fo[head];
+                    if (x != x) x = 0.0;                                                   // centrality.py:282-284
+                    acc += x;
+                }
                 w.dep[v] = acc;
                 w.credit[v] = cr;
             }
