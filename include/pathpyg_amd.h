@@ -979,6 +979,67 @@ int pp_rolling_fill(const void* keys, int key_bytes, const uint32_t* perm, int64
                     int64_t W, int64_t w0, int64_t w1, const int32_t* cnt, int64_t total, int64_t* out_src, int64_t* out_dst, float* out_weight,
                     uint32_t* num_nodes_out, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ graph statistics (pp_graph_triads.hip) */
+/* The sizes of the intersection of two sorted successor lists: what closed_triads / local_clustering_coefficient,
+ * src/pathpyG/statistics/clustering.py:10-88, and the set-based measures of node_similarities.py:39-178 get from Python loops and sets.
+ * All of them read the SIMPLE successor structure of a graph: row_ptr [n + 1] int64, col [ms] int64 strictly increasing inside a row,
+ * row [ms] the row of every entry, mult [ms] int64 the number of stored parallel edges behind an entry (NULL: all 1).  A node index outside
+ * [0, n) is never dereferenced (its list counts as empty); row pointers are clamped to [0, ms].  All pointers but ws contents are DEVICE
+ * pointers; integer results are exact and every result is the same on every run.
+ *
+ * group: the number of lanes that share one pair of lists, a power of two up to 64; 0 = the smallest power of two no less than ms / n,
+ *   between 4 and 64.  heavy_min: a pair whose SHORTER list has this many entries or more goes to a second launch with a workgroup per pair;
+ *   0 = 1024.  Both change the time only, and the last bits of `aa`.
+ *
+ * pp_graph_count_unordered: out [1] = the number of positions e with (row, col)[e] >= (row, col)[e + 1] in edge_index [2, m] int64 row-major:
+ *   0 means the stored list is (row, col)-sorted without parallel edges, i.e. it is its own simple structure.
+ * pp_graph_triad_entry_counts: cnt [e1 - e0], cnt[e - e0] = |S(col[e]) n S(row[e])| for the entries e0 <= e < e1: the closed triads (x, y) of
+ *   v = row[e] with x = col[e], self-loops included as the reference's sets include them.  ws: pp_graph_meet_ws_bytes(e1 - e0).
+ * pp_graph_triad_node_counts: triads [n] = the sum of those counts over each row (a difference of their exclusive scan): the size of
+ *   closed_triads(g, v) for every v.  ws: pp_graph_triad_node_counts_ws_bytes(ms).
+ * pp_graph_pair_meets: for pairs [2, P] int64 row-major (v = pairs[p], w = pairs[P + p]): common[p] = |S(v) n S(w)|, dot[p] (or NULL) = the
+ *   sum of mult_v(u) mult_w(u) over the common u, aa[p] (or NULL) = the sum of table[d(u)] over them, d(u) = deg_ptr[u + 1] - deg_ptr[u] the
+ *   STORED out-degree (deg_ptr [n + 1] int64), table [table_len] float64 (d is clamped to table_len - 1).  The float64 sum has a fixed shape:
+ *   the same bits on every call with the same structure, group and heavy_min, whatever else the batch holds.  sizes [2, P] (or NULL) = the
+ *   lengths of the two lists.  ws: pp_graph_meet_ws_bytes(P).
+ * pp_graph_triad_fill: the closed triads of the one node v as out [2, total] int64 row-major ((x, y) pairs, grouped by x in the order of
+ *   v's row, y ascending); offset [offsets] = the exclusive scan of pp_graph_triad_entry_counts over v's row, total its sum. */
+int pp_graph_count_unordered(const int64_t* edge_index, int64_t m, int64_t* out, pp_stream_t stream);
+size_t pp_graph_meet_ws_bytes(int64_t tasks);
+int pp_graph_triad_entry_counts(const int64_t* row_ptr, const int64_t* row, const int64_t* col, int64_t n, int64_t ms, int64_t e0, int64_t e1,
+                                int group, int64_t heavy_min, int64_t* cnt, void* ws, size_t ws_bytes, pp_stream_t stream);
+size_t pp_graph_triad_node_counts_ws_bytes(int64_t ms);
+int pp_graph_triad_node_counts(const int64_t* row_ptr, const int64_t* row, const int64_t* col, int64_t n, int64_t ms, int group, int64_t heavy_min,
+                               int64_t* triads, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_graph_pair_meets(const int64_t* row_ptr, const int64_t* col, const int64_t* mult, int64_t n, int64_t ms, const int64_t* pairs, int64_t P,
+                        const int64_t* deg_ptr, const double* table, int64_t table_len, int group, int64_t heavy_min, int64_t* common,
+                        int64_t* dot, double* aa, int64_t* sizes, void* ws, size_t ws_bytes, pp_stream_t stream);
+
+/* out [P] float64 = one measure of node_similarities.py per pair, from the integers of pp_graph_pair_meets; NaN where the reference's scalar
+ * function raises ZeroDivisionError.  Each value is an exact integer operation followed by correctly rounded float64 divisions / square roots:
+ *   PP_PAIR_OVERLAP      common / min(sizes)               (NaN when a list is empty)            node_similarities.py:59-80
+ *   PP_PAIR_JACCARD      common / (sizes - common), 1 when both lists are empty                 :83-113
+ *   PP_PAIR_ADAMIC_ADAR  aa, 0 without a common neighbour                                       :116-145
+ *   PP_PAIR_COSINE       dot / (sqrt(norm2[p]) sqrt(norm2[P + p])), norm2 [2, P] = the dot of each node with itself; 0 when the stored
+ *                        in-degree indeg [n] (int32) of either node is 0, as the reference tests it       :148-178 */
+enum { PP_PAIR_OVERLAP = 1, PP_PAIR_JACCARD = 2, PP_PAIR_ADAMIC_ADAR = 3, PP_PAIR_COSINE = 4 };
+int pp_pair_measure(int measure, const int64_t* common, const int64_t* dot, const double* aa, const int64_t* sizes, const int64_t* norm2,
+                    const int32_t* indeg, const int64_t* pairs, int64_t P, int64_t n, double* out, pp_stream_t stream);
+int pp_graph_triad_fill(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t ms, int64_t v, const int64_t* offset, int64_t offsets,
+                        int64_t total, int64_t* out, pp_stream_t stream);
+
+/* out [1] int64 (device) = the sum over the stored edges of a[src] * b[dst] (a == NULL: of b[dst]), a, b [n] int32 degree vectors:
+ * S_e of degree_assortativity, src/pathpyG/statistics/degrees.py:207-247, as an exact integer (int64 adds: the same in any order). */
+int pp_degree_product_sum(const int64_t* edge_index, int64_t m, int64_t n, const int32_t* a, const int32_t* b, int64_t* out, pp_stream_t stream);
+
+/* coeff [n] float64 (or NULL): triads[v] / (deg[v] (deg[v] - 1)), 0 where deg[v] <= 1 — one correctly rounded division of two exact
+ * numbers, which is what local_clustering_coefficient, clustering.py:10-37, evaluates for either kind of graph (its undirected branch halves and
+ * doubles the count).  mean [1] float64 (or NULL): the mean of the coefficients ROUNDED TO float32 (avg_clustering_coefficient, :67), summed
+ * in float64 with a fixed shape and rounded to float32 at the end; NaN for n == 0.  ws: pp_graph_clustering_ws_bytes(). */
+size_t pp_graph_clustering_ws_bytes(void);
+int pp_graph_clustering(const int64_t* triads, const int32_t* deg, int64_t n, double* coeff, double* mean, void* ws, size_t ws_bytes,
+                        pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

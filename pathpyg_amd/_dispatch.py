@@ -107,6 +107,76 @@ def graph_components(graph, strong: bool, with_stats: bool = False):
     return (count, labels, sizes, stats) if with_stats else (count, labels, sizes)
 
 
+def count_unordered(edge_index) -> int:
+    if edge_index.size(1) < 2:
+        return 0
+    dev = compute_device(edge_index)
+    (ei,) = _stage(dev, edge_index)
+    return _hip.count_unordered(ei)
+
+
+def _graph_simple(graph, dev):
+    """The simple successor structure of a Graph (wherever it lives) on the compute device: ``(row_ptr, row, col, mult | None)``."""
+    return _stage(dev, *graph.simple_successors())
+
+
+def graph_triad_counts(graph):
+    """The number of closed triads of every node: int64 ``[n]`` on the compute device (csrc/pp_graph_triads.hip).  A CPU-resident graph
+    is staged, as in :func:`graph_components`."""
+    dev = compute_device(graph.data.edge_index)
+    row_ptr, row, col, _ = _graph_simple(graph, dev)
+    return _hip.graph_triad_node_counts(row_ptr, row, col, graph.n)
+
+
+def graph_triads_of(graph, v: int, want_pairs: bool):
+    """Node ``v`` alone: ``(count, pairs)`` with the closed triads as int64 ``[2, count]`` index pairs on the compute device (``None``
+    unless wanted) — the entry counts of v's row, their scan, the fill."""
+    dev = compute_device(graph.data.edge_index)
+    row_ptr, row, col, _ = _graph_simple(graph, dev)
+    e0, e1 = row_ptr[v:v + 2].tolist()
+    scan = _hip.exclusive_scan(_hip.graph_triad_entry_counts(row_ptr, row, col, graph.n, e0, e1))
+    total = int(scan[-1].item())
+    return total, (_hip.graph_triad_fill(row_ptr, col, graph.n, v, scan, total) if want_pairs else None)
+
+
+def graph_pair_meets(graph, pairs, table=None, want_dot: bool = False, want_sizes: bool = False):
+    """``(common, dot | None, aa | None, sizes | None)`` of the index pairs ``pairs`` [2, P] on the compute device; ``table``: a host float64 array indexed
+    by stored out-degree, which switches ``aa`` on."""
+    dev = compute_device(graph.data.edge_index)
+    row_ptr, _, col, mult = _graph_simple(graph, dev)
+    (pairs,) = _stage(dev, pairs)
+    deg_ptr = None
+    if table is not None:
+        (deg_ptr,) = _stage(dev, graph.row_ptr)
+        table = torch.as_tensor(table, dtype=torch.float64).to(dev)
+    return _hip.graph_pair_meets(row_ptr, col, mult, graph.n, pairs, deg_ptr, table, want_dot, want_sizes)
+
+
+def degree_product_sum(graph, a, b) -> int:
+    dev = compute_device(graph.data.edge_index)
+    ei, a, b = _stage(dev, graph.data.edge_index, a, b)
+    return _hip.degree_product_sum(ei, graph.n, a, b)
+
+
+def graph_clustering(graph, triads, want_coeff: bool, want_mean: bool):
+    """Local coefficients (float64 ``[n]``) and / or the mean of their float32 roundings (float64 ``[1]``) on the compute device, from the
+    degree the reference normalises with: stored out-degrees, stored in-degrees for a graph flagged undirected."""
+    dev = compute_device(graph.data.edge_index)
+    deg = graph.degrees(mode="in" if graph.is_undirected() else "out", return_tensor=True)
+    triads, deg = _stage(dev, triads, deg)
+    return _hip.graph_clustering(triads, deg, want_coeff, want_mean)
+
+
+def degree_histogram(graph, degree_seq):
+    """``bincount`` of a degree sequence as a kernel (``pp_degree_i64``): int32 ``[max degree + 1]`` on the compute device."""
+    dev = compute_device(graph.data.edge_index)
+    (seq,) = _stage(dev, degree_seq)
+    seq = seq.to(torch.int64)
+    if seq.numel() == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev)
+    return _hip.degree(seq, _hip.minmax(seq)[1] + 1)
+
+
 def linegraph_lift(edge_index, num_nodes: int, edge_range=None):
     dev = compute_device(edge_index)
     (ei,) = _stage(dev, edge_index)

@@ -760,6 +760,157 @@ def graph_component_edges(edge_index: torch.Tensor, labels: torch.Tensor, keep: 
         return out[:, :kept].contiguous()
 
 
+# ------------------------------------------------------------------ graph statistics (pp_graph_triads.hip)
+# Work split of the list intersections, None = the library's choice (include/pathpyg_amd.h): the lanes per pair of lists (a power of two up to
+# 64) and the length of the shorter list from which a pair gets a whole workgroup.  They change the time, never an integer result.
+TRIAD_GROUP: int | None = None
+TRIAD_HEAVY_MIN: int | None = None
+
+
+def _triad_split() -> tuple[int, int]:
+    return int(TRIAD_GROUP or 0), int(TRIAD_HEAVY_MIN or 0)
+
+
+def count_unordered(edge_index: torch.Tensor) -> int:
+    """Number of positions at which the stored edge list is not strictly (row, col)-increasing (one 8-byte read-back)."""
+    ei = _edge_index(edge_index)
+    dev = require_device(ei)
+    with torch.cuda.device(dev):
+        out = torch.empty(1, dtype=torch.int64, device=dev)
+        check(lib().pp_graph_count_unordered(_p(ei), ei.size(1), _p(out), _stream()), "pp_graph_count_unordered")
+        return int(out.item())
+
+
+def _simple(row_ptr, row, col, num_nodes: int):
+    row_ptr, row, col = (t.to(torch.int64).contiguous() for t in (row_ptr, row, col))
+    dev = require_device(row_ptr, row, col)
+    n, ms = int(num_nodes), col.numel()
+    if row_ptr.numel() != n + 1 or row.numel() != ms:
+        raise ValueError(f"row_ptr and row must have num_nodes + 1 = {n + 1} and {ms} entries, got {row_ptr.numel()} and {row.numel()}")
+    return row_ptr, row, col, dev, n, ms
+
+
+def graph_triad_entry_counts(row_ptr, row, col, num_nodes: int, e0: int, e1: int) -> torch.Tensor:
+    """``cnt[e - e0] = |S(col[e]) ∩ S(row[e])|`` (int64) for the entries ``e0 <= e < e1`` of a simple successor structure."""
+    row_ptr, row, col, dev, n, ms = _simple(row_ptr, row, col, num_nodes)
+    if not 0 <= e0 <= e1 <= ms:
+        raise IndexError(f"entry range [{e0}, {e1}) outside [0, {ms}]")
+    group, heavy = _triad_split()
+    L = lib()
+    with torch.cuda.device(dev):
+        cnt = torch.empty(e1 - e0, dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_graph_meet_ws_bytes(e1 - e0), dev)
+        check(L.pp_graph_triad_entry_counts(_p(row_ptr), _p(row), _p(col), n, ms, e0, e1, group, heavy, _p(cnt), _p(ws), ws.numel(), _stream()),
+              "pp_graph_triad_entry_counts")
+    return cnt
+
+
+def graph_triad_node_counts(row_ptr, row, col, num_nodes: int) -> torch.Tensor:
+    """The number of closed triads of every node (int64 ``[n]``) from a simple successor structure."""
+    row_ptr, row, col, dev, n, ms = _simple(row_ptr, row, col, num_nodes)
+    group, heavy = _triad_split()
+    L = lib()
+    with torch.cuda.device(dev):
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        ws = _workspace(L.pp_graph_triad_node_counts_ws_bytes(ms), dev)
+        check(L.pp_graph_triad_node_counts(_p(row_ptr), _p(row), _p(col), n, ms, group, heavy, _p(out), _p(ws), ws.numel(), _stream()),
+              "pp_graph_triad_node_counts")
+    return out
+
+
+def graph_triad_fill(row_ptr, col, num_nodes: int, v: int, offset: torch.Tensor, total: int) -> torch.Tensor:
+    """The closed triads of node ``v`` as int64 ``[2, total]``; ``offset`` = the exclusive scan of its row's entry counts."""
+    row_ptr, col, offset = (t.to(torch.int64).contiguous() for t in (row_ptr, col, offset))
+    dev = require_device(row_ptr, col, offset)
+    n = int(num_nodes)
+    if row_ptr.numel() != n + 1:
+        raise ValueError(f"row_ptr must have num_nodes + 1 = {n + 1} entries, got {row_ptr.numel()}")
+    if not 0 <= v < n:
+        raise IndexError(f"node index out of range [0, {n})")
+    with torch.cuda.device(dev):
+        out = torch.empty((2, int(total)), dtype=torch.int64, device=dev)
+        check(lib().pp_graph_triad_fill(_p(row_ptr), _p(col), n, col.numel(), int(v), _p(offset), offset.numel(), int(total), _p(out), _stream()),
+              "pp_graph_triad_fill")
+    return out
+
+
+PAIR_MEASURES = {"overlap": 1, "jaccard": 2, "adamic_adar": 3, "cosine": 4}
+
+
+def pair_measure(measure: str, n: int, pairs, common, dot=None, aa=None, sizes=None, norm2=None, indeg=None) -> torch.Tensor:
+    """float64 ``[P]``: one similarity measure per pair from the integers of :func:`graph_pair_meets` (``pp_pair_measure``)."""
+    dev = require_device(pairs, common, dot, aa, sizes, norm2, indeg)
+    P = common.numel()
+    with torch.cuda.device(dev):
+        out = torch.empty(P, dtype=torch.float64, device=dev)
+        check(lib().pp_pair_measure(PAIR_MEASURES[measure], _p(common), _p(dot), _p(aa), _p(sizes), _p(norm2), _p(indeg), _p(pairs), P, int(n),
+                                    _p(out), _stream()), "pp_pair_measure")
+    return out
+
+
+def graph_pair_meets(row_ptr, col, mult, num_nodes: int, pairs: torch.Tensor, deg_ptr=None, table=None, want_dot: bool = False,
+                     want_sizes: bool = False):
+    """``(common int64 [P], dot int64 [P] | None, aa float64 [P] | None, sizes int64 [2, P] | None)`` for the node index pairs ``pairs`` [2, P] on a simple successor
+    structure; ``aa`` when ``table`` (float64, by stored out-degree) and ``deg_ptr`` (the stored row pointers) are given."""
+    row_ptr, col = row_ptr.to(torch.int64).contiguous(), col.to(torch.int64).contiguous()
+    pairs = _edge_index(pairs)
+    mult = None if mult is None else mult.to(torch.int64).contiguous()
+    dev = require_device(row_ptr, col, mult, pairs, deg_ptr, table)
+    n, ms, P = int(num_nodes), col.numel(), pairs.size(1)
+    if row_ptr.numel() != n + 1 or (mult is not None and mult.numel() != ms):
+        raise ValueError("row_ptr must have num_nodes + 1 entries and mult one per entry of col")
+    if P:
+        lo, hi = minmax(pairs)
+        if lo < 0 or hi >= n:
+            raise IndexError(f"node index out of range [0, {n})")
+    if table is not None:
+        table, deg_ptr = table.to(torch.float64).contiguous(), deg_ptr.to(torch.int64).contiguous()
+        if deg_ptr.numel() != n + 1 or table.numel() < 1:
+            raise ValueError("deg_ptr must have num_nodes + 1 entries and the table at least one")
+    group, heavy = _triad_split()
+    L = lib()
+    with torch.cuda.device(dev):
+        common = torch.empty(P, dtype=torch.int64, device=dev)
+        dot = torch.empty(P, dtype=torch.int64, device=dev) if want_dot else None
+        aa = torch.empty(P, dtype=torch.float64, device=dev) if table is not None else None
+        sizes = torch.empty((2, P), dtype=torch.int64, device=dev) if want_sizes else None
+        ws = _workspace(L.pp_graph_meet_ws_bytes(P), dev)
+        check(L.pp_graph_pair_meets(_p(row_ptr), _p(col), _p(mult), n, ms, _p(pairs), P, _p(deg_ptr), _p(table), 0 if table is None else table.numel(),
+                                    group, heavy, _p(common), _p(dot), _p(aa), _p(sizes), _p(ws), ws.numel(), _stream()), "pp_graph_pair_meets")
+    return common, dot, aa, sizes
+
+
+def degree_product_sum(edge_index: torch.Tensor, num_nodes: int, a: torch.Tensor | None, b: torch.Tensor) -> int:
+    """The exact integer ``sum over stored edges of a[src] * b[dst]`` (``a = None``: of ``b[dst]``); ``a``, ``b`` int32 ``[n]``."""
+    ei = _edge_index(edge_index)
+    a = None if a is None else a.to(torch.int32).contiguous()
+    b = b.to(torch.int32).contiguous()
+    dev = require_device(ei, a, b)
+    n = int(num_nodes)
+    if b.numel() != n or (a is not None and a.numel() != n):
+        raise ValueError(f"degree vectors must have num_nodes = {n} entries")
+    with torch.cuda.device(dev):
+        out = torch.empty(1, dtype=torch.int64, device=dev)
+        check(lib().pp_degree_product_sum(_p(ei), ei.size(1), n, _p(a), _p(b), _p(out), _stream()), "pp_degree_product_sum")
+        return int(out.item())
+
+
+def graph_clustering(triads: torch.Tensor, deg: torch.Tensor, want_coeff: bool = True, want_mean: bool = False):
+    """``(coeff float64 [n] | None, mean float64 [1] | None)`` from the closed-triad counts (int64) and the degrees (int32) of all nodes."""
+    triads, deg = triads.to(torch.int64).contiguous(), deg.to(torch.int32).contiguous()
+    dev = require_device(triads, deg)
+    n = triads.numel()
+    if deg.numel() != n:
+        raise ValueError(f"deg must have {n} entries, got {deg.numel()}")
+    L = lib()
+    with torch.cuda.device(dev):
+        coeff = torch.empty(n, dtype=torch.float64, device=dev) if want_coeff else None
+        mean = torch.empty(1, dtype=torch.float64, device=dev) if want_mean else None
+        ws = _workspace(L.pp_graph_clustering_ws_bytes(), dev)
+        check(L.pp_graph_clustering(_p(triads), _p(deg), n, _p(coeff), _p(mean), _p(ws), ws.numel(), _stream()), "pp_graph_clustering")
+    return coeff, mean
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""

@@ -66,6 +66,7 @@ class Graph:
         self._edge_to_index: Optional[dict] = None
         self._csr: Optional[tuple] = None
         self._csc: Optional[tuple] = None
+        self._simple: Optional[tuple] = None
 
         if "node_sequence" not in data:
             data.node_sequence = torch.arange(n, device=data.edge_index.device).reshape(-1, 1)
@@ -79,7 +80,7 @@ class Graph:
         g.mapping = IndexMap() if mapping is None else mapping
         g.is_undirected_flag = False
         g.data = data
-        g._edge_to_index = g._csr = g._csc = None
+        g._edge_to_index = g._csr = g._csc = g._simple = None
         return g
 
     @staticmethod
@@ -136,6 +137,20 @@ class Graph:
                 self._csc = (_dispatch.ptr_from_sorted(ei[1][perm], self.n), ei[0][perm], perm)
         return self._csc
 
+    def simple_successors(self) -> tuple:
+        """``(row_ptr [n + 1], row [k], col [k], mult [k] | None)``: the successor SETS of all nodes — parallel edges merged, columns strictly
+        increasing inside a row, ``mult`` the number of stored edges behind every entry (``None``: all one) — which the list intersections
+        of :mod:`pathpyg_amd.statistics` read.  A stored list that is strictly (row, col)-increasing already (De Bruijn layers, static
+        aggregates, ``to_undirected()``) is its own structure: one check kernel finds that out; any other list is coalesced once."""
+        if self._simple is None:
+            ei = self.data.edge_index
+            if _dispatch.count_unordered(ei) == 0:
+                self._simple = (self.row_ptr, ei[0], ei[1], None)
+            else:
+                merged, mult = _dispatch.coalesce(ei, torch.ones(ei.size(1), dtype=torch.int64, device=ei.device), self.n, "sum")
+                self._simple = (_dispatch.ptr_from_sorted(merged[0], self.n), merged[0], merged[1], mult)
+        return self._simple
+
     @property
     def row_ptr(self) -> torch.Tensor:
         return self._build_csr()[0]
@@ -170,6 +185,8 @@ class Graph:
             self._csr = tuple(t.to(device) for t in self._csr)
         if self._csc is not None:
             self._csc = tuple(t.to(device) for t in self._csc)
+        if self._simple is not None:
+            self._simple = tuple(None if t is None else t.to(device) for t in self._simple)
         return self
 
     def node_attrs(self) -> list:
