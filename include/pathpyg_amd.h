@@ -1040,6 +1040,35 @@ size_t pp_graph_clustering_ws_bytes(void);
 int pp_graph_clustering(const int64_t* triads, const int32_t* deg, int64_t n, double* coeff, double* mean, void* ws, size_t ws_bytes,
                         pp_stream_t stream);
 
+/* ------------------------------------------------------------------ colour refinement (pp_graph_wl.hip) */
+/* Colour refinement (the 1-dimensional Weisfeiler-Leman iteration) of a static graph on its CSR (row_ptr [n + 1], col [m] int64, device):
+ * the rounds of WeisfeilerLeman_test, src/pathpyG/algorithms/weisfeiler_leman.py:44-62, which build one Python string per node and round.
+ * A node's signature is (own colour, multiset of the colours of its STORED successors): parallel edges count with their multiplicity, a
+ * self-loop contributes the node's own colour, predecessors play no part.  n, m < 2^31 - 1, PP_ERR_TOO_LARGE from there on, before anything is
+ * launched.  A column outside [0, n) is never dereferenced (it counts as one extra colour); row pointers are clamped to [0, m].
+ *   initial [n] int64 (device) or NULL (all nodes equal): any values.  order [n] int64 (device) or NULL (index order): a permutation of
+ *   0 .. n-1, the rank of every node; PP_ERR_ARG if it is none.  max_rounds < 0: refine until the class count stops growing.
+ *   colours [n] int64 (device): the classes after the last round, numbered 0 .. k-1 by the first occurrence of a member in `order`.
+ *   counts, passes [stats_cap] HOST arrays, rounds_out [1] HOST: counts[0] = the number of distinct initial colours, counts[r] the number of
+ *   classes after round r = 1 .. *rounds_out; the last round of an unbounded call is the one that did not grow the count (its partition and
+ *   numbers equal the previous round's).  passes[r] = the verify passes of round r (passes[0]: of the initial grouping, 0 without `initial`).
+ *   n == 0: counts = {0} or, if a round was asked for, {0, 0}.  PP_ERR_ARG if stats_cap < rounds + 1 (n + 2 always suffices).
+ *   seconds [3] HOST or NULL: when given, the stream is drained around every stage and the wall time is added up: [0] keys + sort,
+ *   [1] the signature, election, verify and numbering kernels, [2] the grouping (unique rows).
+ * Exactness: per round the m keys row * (k + 1) + colour[col] are sorted (pp_sort.hip), each node gets (own colour, degree, two 63-bit sums of
+ * mixed colours AND hash_mask), nodes are grouped by these words (pp_unique_rows_count), and every node then compares its sorted row element by
+ * element with that of the group's unresolved node of smallest rank (integer atomicMin); those that differ go through another election.  The
+ * classes are exact for every hash_mask, 0 included; a weaker hash only adds verify passes.
+ * group: the lanes that share one row, a power of two up to 64; 0 = the smallest power of two no less than m / n, between 4 and 64.
+ * heavy_min: a row of this many entries or more gets a whole workgroup in a second launch; 0 = pp_graph_wl_heavy_min() = 1024.  Both change
+ * the time only.  Integer work only: every output is the same on every run.  The round loop is a host loop over launches: the call
+ * synchronises the stream once per verify pass (and once or twice before the first round).  ws: pp_graph_wl_ws_bytes(n, m). */
+int64_t pp_graph_wl_heavy_min(void);
+size_t pp_graph_wl_ws_bytes(int64_t n, int64_t m);
+int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, int64_t m, const int64_t* initial, const int64_t* order,
+                       int64_t max_rounds, int64_t hash_mask, int group, int64_t heavy_min, int64_t* colours, int64_t* counts, int64_t* passes,
+                       int64_t stats_cap, int64_t* rounds_out, double* seconds, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,24 @@ def graph_components(graph, strong: bool, with_stats: bool = False):
     return (count, labels, sizes, stats) if with_stats else (count, labels, sizes)
 
 
+def graph_color_refinement(graph, initial=None, order=None, max_rounds=None, hash_mask: int = -1, timed: bool = False):
+    """``(colours int64 [n] on the compute device, _hip.WlStats)`` of one graph's CSR (csrc/pp_graph_wl.hip).  A CPU-resident graph, and a
+    CPU ``initial`` / ``order``, are staged, as in :func:`graph_components`."""
+    dev = compute_device(graph.data.edge_index)
+    row_ptr, col, initial, order = _stage(dev, graph.row_ptr, graph.col, initial, order)
+    return _hip.graph_wl_refine(row_ptr, col, graph.n, initial, order, max_rounds, hash_mask, timed)
+
+
+def graph_pair_color_refinement(g1, g2, initial=None, order=None, hash_mask: int = -1):
+    """The same on the disjoint union of two graphs: the block-diagonal concatenation of their CSRs on the compute device (the nodes of
+    ``g2`` follow those of ``g1``; no ID is touched, no edge list is rebuilt)."""
+    dev = compute_device(g1.data.edge_index, g2.data.edge_index)
+    ptr1, col1, ptr2, col2, initial, order = _stage(dev, g1.row_ptr, g1.col, g2.row_ptr, g2.col, initial, order)
+    row_ptr = torch.cat((ptr1[:-1], ptr2 + col1.numel()))
+    col = torch.cat((col1, col2 + g1.n))
+    return _hip.graph_wl_refine(row_ptr, col, g1.n + g2.n, initial, order, None, hash_mask)
+
+
 def count_unordered(edge_index) -> int:
     if edge_index.size(1) < 2:
         return 0

@@ -911,6 +911,60 @@ def graph_clustering(triads: torch.Tensor, deg: torch.Tensor, want_coeff: bool =
     return coeff, mean
 
 
+# ------------------------------------------------------------------ colour refinement (pp_graph_wl.hip)
+# Work split of the row walks, None = the library's choice (include/pathpyg_amd.h): the lanes per row (a power of two up to 64) and the row
+# length from which a row gets a whole workgroup.  They change the time, never a result.
+WL_GROUP: int | None = None
+WL_HEAVY_MIN: int | None = None
+
+
+def wl_heavy_min() -> int:
+    """The row length from which colour refinement gives a row a whole workgroup (``WL_HEAVY_MIN`` or the library's default)."""
+    return int(WL_HEAVY_MIN or lib().pp_graph_wl_heavy_min())
+
+
+class WlStats(NamedTuple):
+    counts: list            # counts[r]: classes after round r; counts[0]: distinct initial colours
+    passes: list            # passes[r]: verify passes of round r
+    seconds: "list | None"  # [keys + sort, new kernels, grouping] when timed
+
+
+def graph_wl_refine(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, initial: torch.Tensor | None = None,
+                    order: torch.Tensor | None = None, max_rounds: int | None = None, hash_mask: int = 0xFFFFFFFFFFFFFFFF, timed: bool = False):
+    """Colour refinement on a CSR: ``(colours int64 [n] on the device, WlStats)``; see ``pp_graph_wl_refine`` in the header."""
+    row_ptr, col = row_ptr.to(torch.int64).contiguous(), col.to(torch.int64).contiguous()
+    n, m = int(num_nodes), col.numel()
+    if row_ptr.numel() != n + 1:
+        raise ValueError(f"row_ptr must have num_nodes + 1 = {n + 1} entries, got {row_ptr.numel()}")
+    vectors = []
+    for t, name in ((initial, "initial"), (order, "order")):
+        if t is not None:
+            if t.dtype != torch.int64 or t.numel() != n:
+                raise ValueError(f"{name} must be an int64 vector of num_nodes = {n} entries")
+            t = t.reshape(-1).contiguous()
+        vectors.append(t)
+    initial, order = vectors
+    if max_rounds is not None and max_rounds < 0:
+        raise ValueError("max_rounds must be None or >= 0")
+    dev = require_device(row_ptr, col, initial, order)
+    mask = int(hash_mask) & 0xFFFFFFFFFFFFFFFF
+    mask = mask - (1 << 64) if mask >> 63 else mask                     # (the same 64 bits as an int64)
+    cap = n + 2 if max_rounds is None else min(n, max_rounds) + 2
+    L = lib()
+    with torch.cuda.device(dev):
+        colours = torch.empty(n, dtype=torch.int64, device=dev)
+        counts, passes = (ctypes.c_int64 * cap)(), (ctypes.c_int64 * cap)()
+        rounds = ctypes.c_int64(0)
+        seconds = (ctypes.c_double * 3)() if timed else None
+        ws = _workspace(L.pp_graph_wl_ws_bytes(n, m), dev)
+        check(L.pp_graph_wl_refine(_p(row_ptr), _p(col), n, m, _p(initial), _p(order), -1 if max_rounds is None else int(max_rounds), mask,
+                                   int(WL_GROUP or 0), int(WL_HEAVY_MIN or 0), _p(colours), ctypes.addressof(counts), ctypes.addressof(passes),
+                                   cap, ctypes.addressof(rounds), ctypes.addressof(seconds) if timed else None, _p(ws), ws.numel(), _stream()),
+              "pp_graph_wl_refine")
+    r = rounds.value + 1
+    return colours, WlStats(list(counts[:r]), list(passes[:r]), list(seconds) if timed else None)
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""
