@@ -1069,6 +1069,51 @@ int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, in
                        int64_t max_rounds, int64_t hash_mask, int group, int64_t heavy_min, int64_t* colours, int64_t* counts, int64_t* passes,
                        int64_t stats_cap, int64_t* rounds_out, double* seconds, void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ random graph models (pp_random_graphs.hip)
+ * Reference: src/pathpyG/algorithms/generative_models.py (G(n,p), G(n,m), stochastic block model, Watts-Strogatz), host loops there.
+ * Every random word is one block of Philox4x32-10 keyed by the 64-bit `seed`; the counter is {index lo, index hi, stream lo,
+ * tag << 24 | stream bits 32..55} and each use has its own tag below.  Integer arithmetic only; results do not depend on the grid (which
+ * follows pp_set_launch_share).  uint64 quantities (seed, bound, threshold) travel as the int64 with the same bits.
+ *   pp_rg_region_count / _fill: a Bernoulli subset of R regions of rank space, walked chunk by chunk with geometric skips.  regions
+ *   [R, 8] int64 (device): {first chunk, slots N, log2 of the chunk's slots, skip constant c = -1 / log2(1 - p) with 32 fraction bits (< 2^63),
+ *   kind, columns, row offset, column offset}; kind 0 rectangle (slot = row * columns + col), 1 strict lower triangle (slot = row (row - 1) / 2
+ *   + col), 2 lower triangle with diagonal, 3 square without diagonal (columns = rows - 1, a column >= row is shifted by one).  First chunks
+ *   ascend; a region without chunks shares its first chunk with the next one.  counts [n_chunks] int64; offsets [n_chunks + 1] its exclusive
+ *   scan; rows, cols [total] int64: the edges in chunk order, ascending slots inside a chunk, offsets added; with perm ([n], rank -> node)
+ *   both ends are mapped.  All ranks < n < 2^31 - 1.
+ *   pp_rg_decode: slot -> (row, col) for `count` given slots of one region shape.
+ *   pp_rg_draws: out[i] = the unbiased draw below `below` (uint64, != 0) with index first + i: multiply-high of a word, rejected while the low
+ *   product word is under 2^64 mod below; attempt a of the draw reads stream `round << 32 | a`.
+ *   pp_rg_first / _keep / _compact: the first m distinct values of a draw sequence, from its stable sort by value (value, draw index):
+ *   first_by_draw[d] = 1 where draw d is the first occurrence of its value; with rank = the exclusive scan of that, keep[i] = sorted entry i is
+ *   a first occurrence of rank < m; with pos = the exclusive scan of keep ([count + 1]), out[pos[i]] = value[i] for the kept (cap entries).
+ *   pp_rg_complement: out[o], o < count: the o-th slot that is not in the ascending distinct list excluded[0 .. k).
+ *   pp_rg_keys: keys[i] = rows[i] * n + cols[i].
+ *   pp_rg_ws_edges: the ring lattice of n nodes and s neighbours, edge e = (k - 1) n + v being v -> (v + k) mod n, its column replaced by a
+ *   uniform draw below n where the edge's decision word is under `threshold` (or `always`); undirected: the ends sorted.  rows, cols [n s].
+ *   pp_rg_ws_offenders: from the stable sort (key, edge) of the keys: flag[edge] = 1 for every copy of a key but the one of smallest edge index
+ *   (dups) and for every loop (loops).  pp_rg_ws_redraw: flagged edges get a new column drawn for (edge, round), the ends sorted if undirected. */
+#define PP_RG_TAG_REGION 1
+#define PP_RG_TAG_GNM 2
+#define PP_RG_TAG_WS_DECIDE 3
+#define PP_RG_TAG_WS_TARGET 4
+#define PP_RG_TAG_WS_REPAIR 5
+int pp_rg_region_count(const int64_t* regions, int64_t n_regions, int64_t n_chunks, int64_t seed, int64_t* counts, pp_stream_t stream);
+int pp_rg_region_fill(const int64_t* regions, int64_t n_regions, int64_t n_chunks, int64_t seed, const int64_t* offsets, const int64_t* perm,
+                      int64_t n, int64_t total, int64_t* rows, int64_t* cols, pp_stream_t stream);
+int pp_rg_decode(const int64_t* slots, int64_t count, int kind, int64_t cols, int64_t* rows_out, int64_t* cols_out, pp_stream_t stream);
+int pp_rg_draws(int64_t below, int64_t seed, int tag, int64_t round, int64_t first, int64_t count, int64_t* out, pp_stream_t stream);
+int pp_rg_first(const int64_t* value, const int32_t* draw, int64_t count, int32_t* first_by_draw, pp_stream_t stream);
+int pp_rg_keep(const int64_t* value, const int32_t* draw, const int64_t* rank, int64_t count, int64_t m, int32_t* keep, pp_stream_t stream);
+int pp_rg_compact(const int64_t* value, const int64_t* pos, int64_t count, int64_t cap, int64_t* out, pp_stream_t stream);
+int pp_rg_complement(const int64_t* excluded, int64_t k, int64_t count, int64_t* out, pp_stream_t stream);
+int pp_rg_keys(const int64_t* rows, const int64_t* cols, int64_t count, int64_t n, int64_t* keys, pp_stream_t stream);
+int pp_rg_ws_edges(int64_t n, int64_t s, int64_t seed, int64_t threshold, int always, int undirected, int64_t* rows, int64_t* cols,
+                   pp_stream_t stream);
+int pp_rg_ws_offenders(const int64_t* key, const int32_t* edge, int64_t count, int64_t n, int dups, int loops, int32_t* flag, pp_stream_t stream);
+int pp_rg_ws_redraw(int64_t n, int64_t count, int64_t seed, int64_t round, int undirected, const int32_t* flag, int64_t* rows, int64_t* cols,
+                    pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

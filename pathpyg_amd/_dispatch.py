@@ -125,6 +125,71 @@ def graph_pair_color_refinement(g1, g2, initial=None, order=None, hash_mask: int
     return _hip.graph_wl_refine(row_ptr, col, g1.n + g2.n, initial, order, None, hash_mask)
 
 
+def random_device(device=None) -> torch.device:
+    """Where a random graph is sampled: ``device`` if it names a GPU, else the current one (a host ``device`` only receives the result)."""
+    if device is not None and torch.device(device).type == "cuda":
+        compute_device()
+        d = torch.device(device)
+        return d if d.index is not None else torch.device("cuda", torch.cuda.current_device())
+    return compute_device()
+
+
+def random_regions(rows: list, n_chunks: int, seed: int, n: int, device=None, perm=None):
+    """The edges (int64 ``[2, E]`` on the compute device) of the region descriptors ``rows`` (host lists; csrc/pp_random_graphs.hip)."""
+    dev = random_device(device)
+    table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 8).to(dev)
+    (perm,) = _stage(dev, perm)
+    return _hip.rg_regions_sample(table, n_chunks, seed, n, perm)
+
+
+def random_block_order(z, num_blocks: int, device=None):
+    """``(sizes, perm)`` of a block assignment (staged if it is CPU-resident): the block sizes as a host list and the stable order of the
+    nodes by block (rank -> node) on the compute device."""
+    dev = random_device(device)
+    (z,) = _stage(dev, z)
+    return _hip.degree(z, num_blocks).tolist(), _hip.argsort(z, (0, max(num_blocks - 1, 0)))
+
+
+def random_draws(below: int, seed: int, first: int, count: int, device=None, tag: int = _hip.RG_TAG_GNM):
+    return _hip.rg_draws(below, seed, first, count, random_device(device), tag)
+
+
+def random_first_distinct(values, m: int, bits: int):
+    return _hip.rg_first_distinct(values, m, bits)
+
+
+def random_sorted(values, bits: int):
+    return _hip.sort_pairs(values, None, 0, max(bits, 1))[0] if values.numel() > 1 else values
+
+
+def random_complement(excluded, total: int, device=None):
+    if excluded is None:
+        excluded = torch.empty(0, dtype=torch.int64, device=random_device(device))
+    return _hip.rg_complement(excluded, total)
+
+
+def random_decode(slots, kind: int, cols: int):
+    dev = compute_device(slots)
+    (slots,) = _stage(dev, slots)
+    return _hip.rg_decode(slots, kind, cols)
+
+
+def random_sort_edges(edge_index, n: int):
+    return _hip.rg_sort_edges(edge_index, n)
+
+
+def random_ring(n: int, s: int, seed: int, threshold: int, always: bool, undirected: bool, no_dups: bool, no_loops: bool, max_rounds: int,
+                device=None):
+    """The rewired ring lattice (int64 ``[2, n s]``, unsorted) after as many repair rounds as it takes (one read-back per round)."""
+    edge_index = _hip.rg_ws_edges(n, s, seed, threshold, always, undirected, random_device(device))
+    if no_dups or no_loops:
+        for rnd in range(1, max_rounds + 1):
+            if _hip.rg_ws_repair(edge_index, n, seed, rnd, no_dups, no_loops, undirected) == 0:
+                return edge_index
+        raise RuntimeError(f"watts_strogatz: edges are still to be repaired after {max_rounds} rounds")
+    return edge_index
+
+
 def count_unordered(edge_index) -> int:
     if edge_index.size(1) < 2:
         return 0

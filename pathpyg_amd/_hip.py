@@ -2664,3 +2664,137 @@ def rolling_fill(keys: torch.Tensor, perm: torch.Tensor, num_nodes: int, lo: tor
                                 src.data_ptr(), dst.data_ptr(), weight[offset:].data_ptr(), _p(nn), _p(ws), ws.numel(), _stream()),
               "pp_rolling_fill")
     return index[:, offset:offset + total], weight[offset:offset + total], nn
+
+
+# ------------------------------------------------------------------ random graph models (csrc/pp_random_graphs.hip)
+RG_TAG_REGION, RG_TAG_GNM, RG_TAG_WS_DECIDE, RG_TAG_WS_TARGET, RG_TAG_WS_REPAIR = 1, 2, 3, 4, 5      # PP_RG_TAG_* of the header
+RG_RECT, RG_STRICT, RG_DIAG, RG_NO_DIAG = 0, 1, 2, 3                                                 # region kinds
+
+
+def _i64(v: int) -> int:
+    """The int64 with the bits of the uint64 ``v`` (seeds, bounds and thresholds cross the C ABI as int64)."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= (1 << 63) else v
+
+
+def rg_region_count(regions: torch.Tensor, n_chunks: int, seed: int) -> torch.Tensor:
+    """Edges per chunk (int64 ``[n_chunks]``) of the Bernoulli subsets described by ``regions`` (int64 ``[R, 8]``, see the header)."""
+    dev = require_device(regions)
+    with torch.cuda.device(dev):
+        counts = torch.empty(n_chunks, dtype=torch.int64, device=dev)
+        check(lib().pp_rg_region_count(_p(regions), regions.size(0), n_chunks, _i64(seed), _p(counts), _stream()), "pp_rg_region_count")
+    return counts
+
+
+def rg_region_fill(regions: torch.Tensor, n_chunks: int, seed: int, offsets: torch.Tensor, total: int, n: int,
+                   perm: torch.Tensor | None = None) -> torch.Tensor:
+    """The edges themselves, int64 ``[2, total]`` in chunk order; ``offsets`` is the exclusive scan of :func:`rg_region_count`."""
+    dev = require_device(regions, offsets, perm)
+    with torch.cuda.device(dev):
+        out = torch.empty((2, total), dtype=torch.int64, device=dev)
+        check(lib().pp_rg_region_fill(_p(regions), regions.size(0), n_chunks, _i64(seed), _p(offsets), _p(perm), n, total, out[0].data_ptr(),
+                                      out[1].data_ptr() if total else out.data_ptr(), _stream()), "pp_rg_region_fill")
+    return out
+
+
+def rg_regions_sample(regions: torch.Tensor, n_chunks: int, seed: int, n: int, perm: torch.Tensor | None = None) -> torch.Tensor:
+    """count -> scan -> fill with one read-back (the number of edges)."""
+    if n_chunks == 0:
+        return torch.empty((2, 0), dtype=torch.int64, device=regions.device)
+    offsets = exclusive_scan(rg_region_count(regions, n_chunks, seed))
+    return rg_region_fill(regions, n_chunks, seed, offsets, int(offsets[-1].item()), n, perm)
+
+
+def rg_decode(slots: torch.Tensor, kind: int, cols: int) -> torch.Tensor:
+    """int64 ``[2, k]``: (row, col) of every slot index of one region shape (``RG_*``; ``cols``: the columns of a rectangle)."""
+    slots = slots.contiguous()
+    dev = require_device(slots)
+    k = slots.numel()
+    with torch.cuda.device(dev):
+        out = torch.empty((2, k), dtype=torch.int64, device=dev)
+        check(lib().pp_rg_decode(_p(slots), k, kind, cols, out[0].data_ptr(), out[1].data_ptr() if k else out.data_ptr(), _stream()), "pp_rg_decode")
+    return out
+
+
+def rg_draws(below: int, seed: int, first: int, count: int, device, tag: int = RG_TAG_GNM, round: int = 0) -> torch.Tensor:
+    """The unbiased draws below ``below`` (1 .. 2^64 - 1) with indices ``first .. first + count - 1``; int64 holding the uint64 bits."""
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        out = torch.empty(count, dtype=torch.int64, device=dev)
+        check(lib().pp_rg_draws(_i64(below), _i64(seed), tag, round, first, count, _p(out), _stream()), "pp_rg_draws")
+    return out
+
+
+def rg_first_distinct(values: torch.Tensor, m: int, bits: int):
+    """``(distinct, slots)``: the number of distinct values of the draw sequence ``values`` (non-negative, below ``2**bits``) and, if that
+    reaches ``m``, the first ``m`` distinct ones in ascending order (else ``None``).  One read-back."""
+    dev = require_device(values)
+    k = values.numel()
+    L = lib()
+    sorted_v, draw = sort_pairs(values, None, 0, max(bits, 1))
+    with torch.cuda.device(dev):
+        first = torch.empty(k, dtype=torch.int32, device=dev)
+        check(L.pp_rg_first(_p(sorted_v), _p(draw), k, _p(first), _stream()), "pp_rg_first")
+        rank = exclusive_scan(first)
+        distinct = int(rank[-1].item())
+        if distinct < m:
+            return distinct, None
+        keep = torch.empty(k, dtype=torch.int32, device=dev)
+        check(L.pp_rg_keep(_p(sorted_v), _p(draw), _p(rank), k, m, _p(keep), _stream()), "pp_rg_keep")
+        pos = exclusive_scan(keep)
+        out = torch.empty(m, dtype=torch.int64, device=dev)
+        check(L.pp_rg_compact(_p(sorted_v), _p(pos), k, m, _p(out), _stream()), "pp_rg_compact")
+    return distinct, out
+
+
+def rg_complement(excluded: torch.Tensor, total: int) -> torch.Tensor:
+    """The slots of ``[0, total)`` outside the ascending distinct list ``excluded``, ascending."""
+    dev = require_device(excluded)
+    k = excluded.numel()
+    with torch.cuda.device(dev):
+        out = torch.empty(total - k, dtype=torch.int64, device=dev)
+        check(lib().pp_rg_complement(_p(excluded), k, total - k, _p(out), _stream()), "pp_rg_complement")
+    return out
+
+
+def rg_sorted_keys(edge_index: torch.Tensor, n: int):
+    """``(keys, order)``: the keys ``row * n + col`` in ascending order (stable) and, per sorted key, the position of its edge (int32)."""
+    ei = edge_index.contiguous()
+    dev = require_device(ei)
+    k = ei.size(1)
+    with torch.cuda.device(dev):
+        keys = torch.empty(k, dtype=torch.int64, device=dev)
+        check(lib().pp_rg_keys(ei[0].data_ptr(), ei[1].data_ptr() if k else ei.data_ptr(), k, n, _p(keys), _stream()), "pp_rg_keys")
+    return sort_pairs(keys, None, 0, max((max(n, 1) * max(n, 1) - 1).bit_length(), 1))
+
+
+def rg_sort_edges(edge_index: torch.Tensor, n: int) -> torch.Tensor:
+    """The edges sorted by (row, col); duplicates stay."""
+    _, order = rg_sorted_keys(edge_index, n)
+    return edge_index[:, order.to(torch.int64)].contiguous()
+
+
+def rg_ws_edges(n: int, s: int, seed: int, threshold: int, always: bool, undirected: bool, device) -> torch.Tensor:
+    dev = torch.device(device)
+    with torch.cuda.device(dev):
+        out = torch.empty((2, n * s), dtype=torch.int64, device=dev)
+        check(lib().pp_rg_ws_edges(n, s, _i64(seed), _i64(threshold), int(always), int(undirected), out[0].data_ptr(),
+                                   out[1].data_ptr() if n * s else out.data_ptr(), _stream()), "pp_rg_ws_edges")
+    return out
+
+
+def rg_ws_repair(edge_index: torch.Tensor, n: int, seed: int, round: int, dups: bool, loops: bool, undirected: bool) -> int:
+    """One repair round in place: the surplus copies of an edge (``dups``) and the loops (``loops``) get a new second endpoint drawn for
+    (edge position, ``round``).  Returns the number of offenders it found (0: nothing was changed)."""
+    dev = require_device(edge_index)
+    k = edge_index.size(1)
+    sorted_k, order = rg_sorted_keys(edge_index, n)
+    L = lib()
+    with torch.cuda.device(dev):
+        flag = torch.empty(k, dtype=torch.int32, device=dev)
+        check(L.pp_rg_ws_offenders(_p(sorted_k), _p(order), k, n, int(dups), int(loops), _p(flag), _stream()), "pp_rg_ws_offenders")
+        offenders = int(exclusive_scan(flag)[-1].item())
+        if offenders:
+            check(L.pp_rg_ws_redraw(n, k, _i64(seed), round, int(undirected), _p(flag), edge_index[0].data_ptr(), edge_index[1].data_ptr(), _stream()),
+                  "pp_rg_ws_redraw")
+    return offenders

@@ -1,5 +1,5 @@
 """Algorithms on the hot path of pathpyG: order lifts, De Bruijn aggregation, shortest paths and centralities."""
-from . import centrality, components, shortest_paths, weisfeiler_leman  # noqa: F401
+from . import centrality, components, generative_models, shortest_paths, weisfeiler_leman  # noqa: F401
 from .components import connected_components, largest_connected_component  # noqa: F401
 from .weisfeiler_leman import WeisfeilerLeman_test, color_refinement  # noqa: F401
 from .centrality import (  # noqa: F401
