@@ -1114,6 +1114,36 @@ int pp_rg_ws_offenders(const int64_t* key, const int32_t* edge, int64_t count, i
 int pp_rg_ws_redraw(int64_t n, int64_t count, int64_t seed, int64_t round, int undirected, const int32_t* flag, int64_t* rows, int64_t* cols,
                     pp_stream_t stream);
 
+/* ------------------------------------------------------------------ power-iteration centralities (pp_graph_power.hip) */
+/* eigenvector_centrality and katz_centrality as networkx 3.4 iterates them (the reference forwards both names to networkx on a DiGraph copy,
+ * src/pathpyG/algorithms/centrality.py:327-356), on the PREDECESSOR lists of the distinct edges: col_ptr [n + 1], row [k] int64 (device),
+ * weight [k] float64 or NULL (every entry 1).  n, k < 2^31 - 1.  A row index outside [0, n) is not dereferenced (it adds 0); pointers are
+ * clamped to [0, k].  All values float64.
+ *   PP_POWER_EIGENVECTOR: x0 = start / sum(start) (start == NULL: all ones); y[v] = x[v] + sum_u w(u, v) x[u]; norm = sqrt(sum y^2), 1 if that
+ *     is 0; x' = y / norm; err = sum |x' - x|.  alpha, beta, beta_scalar and normalized are not read.
+ *   PP_POWER_KATZ: x0 = start (NULL: zeros); x'[v] = alpha * (sum_u w(u, v) x[u]) + b[v], b = beta [n] or, if NULL, beta_scalar;
+ *     err = sum |x' - x|.  values = x' * (1 / sqrt(sum x'^2)) if normalized and that norm is not 0, else x'.
+ * The iteration stops at the FIRST iterate with err < threshold (false for a NaN err) or after max_iter >= 1 iterations.  values [n]
+ * (device): that iterate, or the last one.  iterations, converged, grids [2] are HOST words: iterations done, the criterion held, and the
+ * workgroups of the light and the heavy gather launch.
+ * Launch scheme: one iteration is 2 to 4 plain launches (gather of the light rows, gather of the heavy rows if there are any, [eigenvector:
+ * scale and error], decide): Katz 2, or 3 with heavy rows; eigenvector 3, or 4 with heavy rows.  No cooperative launch, no grid-wide barrier, no floating-point atomics.  The decision is taken on the device by
+ * the one-workgroup decide kernel; every kernel reads the device's `done` word first and does nothing once it is set.  The host enqueues
+ * `batch` iterations (0 = 16; otherwise >= 8; the last batch is cut to what max_iter leaves), synchronises the stream and reads {done,
+ * iterations, buffer} once per batch.
+ * Summation: a light row is summed by `group` lanes (a power of two up to 64; 0 = the smallest power of two no less than k / n, between 4
+ * and 64), lane j adding entries j, j + group, ... in order, the lanes folded by a butterfly; a row of heavy_min entries or more (0 =
+ * pp_graph_power_heavy_min() = 1024) by a whole workgroup in a second launch, thread j adding entries j, j + 256, ... .  sum y^2 and the
+ * errors are per-workgroup partials of fixed shape, folded by workgroup index in a fixed shape.  Grids depend on n, group and the number of
+ * heavy rows only: every output has the same bits on every run with the same graph and parameters.  ws: pp_graph_power_ws_bytes(n). */
+enum { PP_POWER_EIGENVECTOR = 0, PP_POWER_KATZ = 1 };
+int64_t pp_graph_power_heavy_min(void);
+size_t pp_graph_power_ws_bytes(int64_t n);
+int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const double* weight, int64_t n, int64_t k, int mode, double alpha,
+                           const double* beta, double beta_scalar, const double* start, int normalized, double threshold, int64_t max_iter,
+                           int64_t batch, int group, int64_t heavy_min, double* values, int64_t* iterations, int64_t* converged, int64_t* grids,
+                           void* ws, size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,36 @@ def graph_pair_color_refinement(g1, g2, initial=None, order=None, hash_mask: int
     return _hip.graph_wl_refine(row_ptr, col, g1.n + g2.n, initial, order, None, hash_mask)
 
 
+POWER_EIGENVECTOR, POWER_KATZ = _hip.POWER_EIGENVECTOR, _hip.POWER_KATZ
+
+
+def graph_entry_weights(graph, attr: str, dev) -> torch.Tensor:
+    """float64 ``[k]`` on ``dev``: the edge attribute ``attr`` summed over the parallel edges behind every entry of
+    ``graph.simple_successors()``, in that structure's order."""
+    values = torch.as_tensor(graph.data[attr]).reshape(-1).to(dev).to(torch.float64)
+    if graph.simple_successors()[3] is None:                            # (the stored list is its own simple structure)
+        return values
+    (ei,) = _stage(dev, graph.data.edge_index)
+    return _hip.coalesce(ei, values, graph.n, "sum")[1]
+
+
+def graph_power_centrality(graph, mode: int, threshold: float, max_iter: int, alpha: float = 0.0, beta=0.0, start=None,
+                           normalized: bool = True, weight: str | None = None, group: int = 0, heavy_min: int = 0, batch: int = 0,
+                           with_stats: bool = False):
+    """``(values float64 [n] on the compute device, iterations, converged)`` of the power iteration ``mode`` (``_hip.POWER_EIGENVECTOR`` /
+    ``_hip.POWER_KATZ``; csrc/pp_graph_power.hip) over ``graph.simple_predecessors()``; with ``with_stats`` the ``_hip.PowerStats`` follow.
+    ``weight`` names an edge attribute (summed over parallel edges) or is ``None`` (every distinct edge counts 1); ``beta`` is a number or
+    a float64 ``[n]`` tensor, ``start`` a float64 ``[n]`` tensor or ``None``.  ``group``, ``heavy_min``, ``batch``: 0 = the library's
+    choice; they never change which iterate is returned.  A CPU-resident graph and CPU vectors are staged, as in :func:`graph_components`."""
+    dev = compute_device(graph.data.edge_index)
+    col_ptr, row, perm = _stage(dev, *graph.simple_predecessors())
+    w = None if weight is None else graph_entry_weights(graph, weight, dev)[perm]
+    beta, start = (t.to(dev).to(torch.float64) if isinstance(t, torch.Tensor) else t for t in (beta, start))
+    values, stats = _hip.graph_power_iterate(col_ptr, row, w, graph.n, mode, threshold, max_iter, alpha, beta, start, normalized, group,
+                                             heavy_min, batch)
+    return (values, stats.iterations, stats.converged, stats) if with_stats else (values, stats.iterations, stats.converged)
+
+
 def random_device(device=None) -> torch.device:
     """Where a random graph is sampled: ``device`` if it names a GPU, else the current one (a host ``device`` only receives the result)."""
     if device is not None and torch.device(device).type == "cuda":

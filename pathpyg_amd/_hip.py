@@ -965,6 +965,56 @@ def graph_wl_refine(row_ptr: torch.Tensor, col: torch.Tensor, num_nodes: int, in
     return colours, WlStats(list(counts[:r]), list(passes[:r]), list(seconds) if timed else None)
 
 
+# ------------------------------------------------------------------ power-iteration centralities (pp_graph_power.hip)
+POWER_EIGENVECTOR, POWER_KATZ = 0, 1
+
+
+def power_heavy_min() -> int:
+    """The predecessor-list length from which the power iteration gives a row a whole workgroup (the library's default)."""
+    return int(lib().pp_graph_power_heavy_min())
+
+
+class PowerStats(NamedTuple):
+    iterations: int         # iterations done
+    converged: bool         # the L1 criterion held at that iteration
+    light_grid: int         # workgroups of the light gather launch
+    heavy_grid: int         # workgroups of the heavy gather launch (0: no row reached heavy_min)
+
+
+def graph_power_iterate(col_ptr: torch.Tensor, row: torch.Tensor, weight: torch.Tensor | None, num_nodes: int, mode: int, threshold: float,
+                        max_iter: int, alpha: float = 0.0, beta: torch.Tensor | float = 0.0, start: torch.Tensor | None = None,
+                        normalized: bool = True, group: int = 0, heavy_min: int = 0, batch: int = 0):
+    """Power iteration on predecessor lists: ``(values float64 [n] on the device, PowerStats)``; see ``pp_graph_power_iterate`` in the
+    header.  ``group``, ``heavy_min`` and ``batch``: 0 = the library's choice."""
+    col_ptr, row = col_ptr.to(torch.int64).contiguous(), row.to(torch.int64).contiguous()
+    n, k = int(num_nodes), row.numel()
+    if col_ptr.numel() != n + 1:
+        raise ValueError(f"col_ptr must have num_nodes + 1 = {n + 1} entries, got {col_ptr.numel()}")
+    beta_vec = beta if isinstance(beta, torch.Tensor) else None
+    vectors = []
+    for t, name, size in ((weight, "weight", k), (beta_vec, "beta", n), (start, "start", n)):
+        if t is not None:
+            if t.dtype != torch.float64 or t.numel() != size:
+                raise ValueError(f"{name} must be a float64 vector of {size} entries")
+            t = t.reshape(-1).contiguous()
+        vectors.append(t)
+    weight, beta_vec, start = vectors
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    dev = require_device(col_ptr, row, weight, beta_vec, start)
+    L = lib()
+    with torch.cuda.device(dev):
+        values = torch.empty(n, dtype=torch.float64, device=dev)
+        iterations, converged, grids = ctypes.c_int64(0), ctypes.c_int64(0), (ctypes.c_int64 * 2)()
+        ws = _workspace(L.pp_graph_power_ws_bytes(n), dev)
+        check(L.pp_graph_power_iterate(_p(col_ptr), _p(row), _p(weight), n, k, int(mode), float(alpha), _p(beta_vec),
+                                       0.0 if beta_vec is not None else float(beta), _p(start), int(bool(normalized)), float(threshold),
+                                       int(max_iter), int(batch), int(group), int(heavy_min), _p(values), ctypes.addressof(iterations),
+                                       ctypes.addressof(converged), ctypes.addressof(grids), _p(ws), ws.numel(), _stream()),
+              "pp_graph_power_iterate")
+    return values, PowerStats(int(iterations.value), bool(converged.value), int(grids[0]), int(grids[1]))
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""

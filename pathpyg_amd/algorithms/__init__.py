@@ -5,6 +5,8 @@ from .weisfeiler_leman import WeisfeilerLeman_test, color_refinement  # noqa: F4
 from .centrality import (  # noqa: F401
     betweenness_centrality,
     closeness_centrality,
+    eigenvector_centrality,
+    katz_centrality,
     map_to_nodes,
     path_node_traversals,
     path_visitation_probabilities,

@@ -16,13 +16,17 @@ The static functions run breadth-first searches on the graph's CSR on the GPU (`
 csrc/pp_graph_paths.hip); the temporal ones live in :mod:`pathpyg_amd.algorithms.temporal` and are re-exported here.  They take any
 :class:`~pathpyg_amd.core.graph.Graph` on any device; edge weights are ignored and every stored edge counts, as in the reference.
 
-Not ported: the reference module's ``__getattr__``, which forwards every unknown name to ``networkx.algorithms.centrality`` on a
-Python copy of the graph.  This package has no networkx dependency and no CPU path, so an unknown name is an ``AttributeError``.
+The reference module's ``__getattr__`` forwards every unknown name to ``networkx.algorithms.centrality`` on a Python copy of the graph.
+Two of the measures behind that forwarding are native here: :func:`eigenvector_centrality` and :func:`katz_centrality` run networkx's
+power iterations as pull products over the predecessor lists of the distinct edges, convergence test included, on the GPU
+(``pp_graph_power_iterate``, csrc/pp_graph_power.hip).  The forwarding itself is not ported: this package has no networkx dependency and
+no CPU path, so every other forwarded name — ``degree_centrality`` included — is an ``AttributeError``.
 """
 from __future__ import annotations
 
 from collections import defaultdict
 
+import numpy as np
 import torch
 
 from .. import _dispatch
@@ -125,3 +129,104 @@ def path_visitation_probabilities(paths) -> dict:
     counts = path_node_traversals(paths)
     total = float(sum(counts.values()))             # integer counts: exact in any order
     return {node: count / total for node, count in counts.items()}
+
+
+class PowerIterationFailedConvergence(RuntimeError):
+    """A power iteration did not meet its criterion within ``max_iter`` iterations (networkx's exception of the same name; this package
+    does not depend on networkx, so the class is its own)."""
+
+    def __init__(self, max_iter: int):
+        self.max_iter = int(max_iter)
+        super().__init__(f"power iteration failed to converge within {self.max_iter} iterations")
+
+
+def _node_vector(value, n: int, name: str) -> torch.Tensor:
+    """``value`` (a 1-D tensor or ndarray of length ``n`` in index order, or a dict keyed by node INDEX — the reference's form: its networkx
+    copy is index-keyed) as a float64 ``[n]`` tensor on the device it came from."""
+    if isinstance(value, dict):
+        missing = [i for i in range(n) if i not in value]
+        if missing or len(value) != n:
+            raise ValueError(f"{name} must have a value for every node index 0 .. {n - 1} and no other key"
+                             + (f" (node index {missing[0]} is missing)" if missing else ""))
+        return torch.tensor([float(value[i]) for i in range(n)], dtype=torch.float64)
+    if isinstance(value, (np.ndarray, list, tuple)):
+        value = torch.as_tensor(np.asarray(value, dtype=np.float64))
+    if not isinstance(value, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, an ndarray or a dict keyed by node index, got {type(value).__name__}")
+    if value.dim() != 1 or value.numel() != n:
+        raise ValueError(f"{name} must be a vector with one entry per node ({n}), got shape {tuple(value.shape)}")
+    return value.to(torch.float64)
+
+
+def _check_power_arguments(graph, max_iter: int, weight) -> None:
+    if int(max_iter) < 1:
+        raise ValueError(f"max_iter must be >= 1, got {max_iter}")
+    if weight is not None:
+        if weight not in graph.edge_attrs():
+            raise KeyError(f"the graph has no edge attribute {weight!r} (it has {graph.edge_attrs()})")
+        shape, m = tuple(np.shape(graph.data[weight])), graph.data.edge_index.size(1)
+        if len(shape) < 1 or shape[0] != m or int(np.prod(shape)) != m:
+            raise ValueError(f"edge attribute {weight!r} must hold one number per stored edge ({m}), got shape {shape}")
+
+
+def _power_result(graph, values: torch.Tensor, converged: bool, max_iter: int, return_tensor: bool):
+    if not converged:
+        raise PowerIterationFailedConvergence(max_iter)
+    return values if return_tensor else dict(zip(_node_ids(graph), values.tolist()))
+
+
+def eigenvector_centrality(graph, max_iter: int = 100, tol: float = 1e-06, nstart=None, weight: str | None = None, *,
+                           return_tensor: bool = False):
+    """Eigenvector centrality as the reference returns it (centrality.py:327-356 forwards to ``networkx.eigenvector_centrality`` on a
+    DiGraph copy): the left eigenvector by power iteration with ``A + I`` over the DISTINCT stored edges — parallel edges collapse,
+    self-loops stay, the undirected flag plays no part.  From ``x = nstart / sum(nstart)`` (default: all ones) every iteration computes
+    ``y[v] = x[v] + sum_{u in pred(v)} w(u, v) x[u]``, divides by ``sqrt(sum y^2)`` (by 1 if that is 0) and stops at the first iterate
+    whose L1 distance to the previous one is below ``n * tol``; networkx's arguments, order and defaults.
+
+    ``nstart``: a 1-D tensor or ndarray of length ``n`` in index order, or a dict keyed by node INDEX (the reference's form).  Results are
+    pinned for non-negative values; any other vector still ends by ``max_iter``.  ``weight=None`` is the reference.  A string ``weight``
+    names an edge attribute of the graph (``"edge_weight"``): an entry's weight is the float64 sum of the attribute over its parallel edges
+    — an extension: the reference's copy carries no attributes, so there every ``weight=`` silently reads 1.
+
+    Returns ``{node id: float}`` for all nodes in index order (one read-back), or with ``return_tensor=True`` the float64 ``[n]`` tensor on
+    the compute device.  Raises ``ValueError`` for the null graph, an all-zero ``nstart``, a vector of the wrong length or a dict that lacks
+    a node, ``KeyError`` for an unknown attribute, :class:`PowerIterationFailedConvergence` after ``max_iter`` iterations without
+    convergence.  Everything runs on the GPU (csrc/pp_graph_power.hip); the result has the same bits on every run."""
+    n = graph.n
+    if n == 0:
+        raise ValueError("cannot compute centrality for the null graph")
+    _check_power_arguments(graph, max_iter, weight)
+    start = None
+    if nstart is not None:
+        start = _node_vector(nstart, n, "nstart")
+        if bool((start == 0).all()):
+            raise ValueError("initial vector cannot have all zero values")
+    values, _, converged = _dispatch.graph_power_centrality(graph, _dispatch.POWER_EIGENVECTOR, n * tol, int(max_iter), start=start,
+                                                     weight=weight)
+    return _power_result(graph, values, converged, max_iter, return_tensor)
+
+
+def katz_centrality(graph, alpha: float = 0.1, beta=1.0, max_iter: int = 1000, tol: float = 1e-06, nstart=None, normalized: bool = True,
+                    weight: str | None = None, *, return_tensor: bool = False):
+    """Katz centrality as the reference returns it (centrality.py:327-356 forwards to ``networkx.katz_centrality`` on a DiGraph copy):
+    from ``x = nstart`` (default: zeros) every iteration computes ``x'[v] = alpha * sum_{u in pred(v)} w(u, v) x[u] + beta[v]`` over the
+    DISTINCT stored edges and stops at the first iterate with ``sum |x' - x| < n * tol``; the result is ``x' / sqrt(sum x'^2)`` if
+    ``normalized`` (and that norm is not 0), else ``x'``.  networkx's arguments, order and defaults.
+
+    ``beta``: a number for every node, or one value per node; it and ``nstart`` take the forms :func:`eigenvector_centrality` describes,
+    and ``weight`` means the same (a named attribute is an extension; ``None`` is the reference).  ``alpha`` at or beyond the reciprocal
+    of the largest eigenvalue diverges: the values overflow, the error becomes NaN, which is not below the threshold, and the call raises
+    after ``max_iter`` iterations.
+
+    Returns ``{node id: float}`` in index order or, with ``return_tensor=True``, the float64 ``[n]`` tensor on the compute device.  For the null
+    graph nothing is computed: ``{}``, or an empty float64 tensor on the device the graph lives on (the host for a CPU-resident graph).
+    Raises as :func:`eigenvector_centrality` does (no all-zero refusal: zeros are the default start)."""
+    n = graph.n
+    _check_power_arguments(graph, max_iter, weight)
+    if n == 0:
+        return torch.empty(0, dtype=torch.float64, device=graph.device) if return_tensor else {}
+    b = float(beta) if isinstance(beta, (int, float, np.integer, np.floating)) else _node_vector(beta, n, "beta")
+    start = None if nstart is None else _node_vector(nstart, n, "nstart")
+    values, _, converged = _dispatch.graph_power_centrality(graph, _dispatch.POWER_KATZ, n * tol, int(max_iter), alpha=float(alpha),
+                                                     beta=b, start=start, normalized=bool(normalized), weight=weight)
+    return _power_result(graph, values, converged, max_iter, return_tensor)

@@ -67,6 +67,7 @@ class Graph:
         self._csr: Optional[tuple] = None
         self._csc: Optional[tuple] = None
         self._simple: Optional[tuple] = None
+        self._simple_pred: Optional[tuple] = None
 
         if "node_sequence" not in data:
             data.node_sequence = torch.arange(n, device=data.edge_index.device).reshape(-1, 1)
@@ -80,7 +81,7 @@ class Graph:
         g.mapping = IndexMap() if mapping is None else mapping
         g.is_undirected_flag = False
         g.data = data
-        g._edge_to_index = g._csr = g._csc = g._simple = None
+        g._edge_to_index = g._csr = g._csc = g._simple = g._simple_pred = None
         return g
 
     @staticmethod
@@ -151,6 +152,21 @@ class Graph:
                 self._simple = (_dispatch.ptr_from_sorted(merged[0], self.n), merged[0], merged[1], mult)
         return self._simple
 
+    def simple_predecessors(self) -> tuple:
+        """``(col_ptr [n + 1], row [k], perm [k])``: the transpose of :meth:`simple_successors` — the predecessor SETS of all nodes, sources
+        ascending inside a list — which the pull products of the power-iteration centralities read.  ``perm[j]`` is the position of entry
+        ``j`` in the simple successor structure, so its ``mult`` (or a weight summed per entry) is gathered with it.  One stable sort of the
+        ``k`` distinct edges by column, done once and kept."""
+        if self._simple_pred is None:
+            _, row, col, _ = self.simple_successors()
+            if col.numel() == 0:
+                empty = torch.empty(0, dtype=torch.int64, device=col.device)
+                self._simple_pred = (torch.zeros(self.n + 1, dtype=torch.int64, device=col.device), empty, empty)
+            else:
+                perm = _dispatch.stable_argsort(col, (0, max(self.n - 1, 0)))
+                self._simple_pred = (_dispatch.ptr_from_sorted(col[perm], self.n), row[perm], perm)
+        return self._simple_pred
+
     @property
     def row_ptr(self) -> torch.Tensor:
         return self._build_csr()[0]
@@ -187,6 +203,8 @@ class Graph:
             self._csc = tuple(t.to(device) for t in self._csc)
         if self._simple is not None:
             self._simple = tuple(None if t is None else t.to(device) for t in self._simple)
+        if self._simple_pred is not None:
+            self._simple_pred = tuple(t.to(device) for t in self._simple_pred)
         return self
 
     def node_attrs(self) -> list:
