@@ -62,6 +62,9 @@ __device__ __forceinline__ float rl_f(float v, int lane) { return __builtin_bit_
 __device__ __forceinline__ uint64_t rl_u64(uint64_t v, int lane) {
     return ((uint64_t)rl_u((uint32_t)(v >> 32), lane) << 32) | (uint64_t)rl_u((uint32_t)v, lane);
 }
+// `old` with the wave-uniform value v in lane `lane` (wave-uniform): v_writelane_b32 (the compiler offers the intrinsic but no builtin for it)
+extern "C" __device__ int pp_llvm_writelane_i32(int v, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+__device__ __forceinline__ int wl_i(int v, int lane, int old) { return pp_llvm_writelane_i32(v, lane, old); }
 // value pushed to lane `dest` (a permutation of the lanes)
 __device__ __forceinline__ uint32_t push_u(int dest, uint32_t v) { return (uint32_t)__builtin_amdgcn_ds_permute(dest << 2, (int)v); }
 __device__ __forceinline__ uint64_t push_u64(int dest, uint64_t v) {
@@ -168,7 +171,13 @@ __global__ __launch_bounds__(kBlock) void k_db2_unzip(int64_t n, const uint2* __
 #define PP_DB2_MID_NODES 1
 #endif
 constexpr int kDb2OutNodes = PP_DB2_OUT_NODES;      // nodes per wave of k_db2_out
-constexpr int kDb2Nodes = PP_DB2_MID_NODES;         // nodes per wave of k_db2_mid
+constexpr int kDb2Nodes = PP_DB2_MID_NODES;         // nodes per wave of k_db2_mid, one after the other (PP_DB2_MID_PAIR 0)
+// k_db2_mid works on TWO nodes per wave side by side (lanes 0-31 / 32-63) where both have at most 32 in- and 32 out-events and take the fast
+// paths; every other pair runs the one-node code twice.  0 compiles the one-node kernel alone (same-box A/B builds)
+#ifndef PP_DB2_MID_PAIR
+#define PP_DB2_MID_PAIR 1
+#endif
+constexpr int kDb2MidPerWave = PP_DB2_MID_PAIR ? 2 : kDb2Nodes;
 
 template <bool kW>
 struct Db2OutIn {
@@ -446,15 +455,14 @@ struct Db2MidIn {
     int simple;
 };
 
-template <typename TimeT, int kMode, bool kFill, bool kW>
-__global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, double delta_f, Db2Mid a) {
+// kN nodes of one wave, one after the other (every node that is not worked on in a pair, see db2_mid_pair)
+template <typename TimeT, int kMode, bool kFill, bool kW, int kN>
+__device__ __forceinline__ void db2_mid_seq(int64_t node0, int64_t n, int64_t delta_i, double delta_f, const Db2Mid& a) {
     using W = Window<TimeT, kMode>;
-    const int64_t node0 = ((int64_t)blockIdx.x * kWavesPerBlock + wave_id()) * kDb2Nodes;
-    if (node0 >= n) return;
     const int l = lane_id();
-    Db2MidIn<kFill, kW> in[kDb2Nodes];
+    Db2MidIn<kFill, kW> in[kN];
 #pragma unroll
-    for (int s = 0; s < kDb2Nodes; ++s) {
+    for (int s = 0; s < kN; ++s) {
         const int64_t node = node0 + s;
         const bool there = node < n;
         const int64_t gn = a.lo + node;
@@ -473,7 +481,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
         }
     }
 #pragma unroll
-    for (int s = 0; s < kDb2Nodes; ++s) {
+    for (int s = 0; s < kN; ++s) {
         const bool fits = in[s].no <= kWave && in[s].ni <= kWave;
         const bool lo_ = fits && l < in[s].no, li = fits && l < in[s].ni;
         in[s].tj = lo_ ? a.ot_s[in[s].p0 + l] : 0ull;
@@ -507,7 +515,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
     }
     if (kFill) {
 #pragma unroll
-        for (int s = 0; s < kDb2Nodes; ++s) {
+        for (int s = 0; s < kN; ++s) {
             // what the fill pass needs per in-event: d^-1/2 of its order-2 row and of its source node, the start of that row's source-major entries — two
             // random reads per lane, issued for all four nodes at once and hidden behind the other waves' instruction issue (round 4: they were a
             // kernel of their own, 0.25 ms of pure latency)
@@ -528,7 +536,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
             }
         }
 #pragma unroll
-        for (int s = 0; s < kDb2Nodes; ++s) {
+        for (int s = 0; s < kN; ++s) {
             const bool lo_ = in[s].no <= kWave && in[s].ni <= kWave && l < in[s].no;
             in[s].rdeg = lo_ ? a.ho_deg[in[s].rid] : 1.0f;
             in[s].rlw = lo_ ? a.ho_lw[in[s].rid] : 1.0f;
@@ -536,7 +544,7 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
         }
     }
 #pragma unroll
-    for (int s = 0; s < kDb2Nodes; ++s) {
+    for (int s = 0; s < kN; ++s) {
         const int64_t node = node0 + s;
         if (node >= n) break;
         const uint32_t gnode = (uint32_t)(a.lo + node);
@@ -770,6 +778,263 @@ __global__ __launch_bounds__(kBlock) void k_db2_mid(int64_t n, int64_t delta_i, 
             if (l == 0 && a.self1) a.self1[node] = d1b * in[s].lw1 * d1b;
         }
     }
+}
+
+// ---- two nodes per wave, side by side.  Lanes 0-31 are the events of node0, lanes 32-63 those of node0 + 1: h = half, ll = lane within the half.
+// What db2_mid_seq holds once per wave (list starts, lengths, row block, node values) is a per-lane value here, equal across a half; a ballot
+// carries both nodes' masks and a lane uses its own half, shifted to bits 0-31; a lane read of position z goes to lane 32 h + z; loops run to the
+// longer list of the two and the half that is done contributes nothing.  Only the fast paths exist in this form: the count pass of nodes whose
+// in-events come from distinct sources and reach no successor run twice, the fill pass of simple nodes.  Every sum runs in the order of
+// db2_mid_seq and run_em keeps its meaning (bit = position of the run's first out-event within the node), so a node may be counted in a pair and
+// filled alone or the reverse.  Returns false, having stored nothing db2_mid_seq does not store again, where the pair has to take that route.
+__device__ __forceinline__ uint32_t half_below(int x) { return (uint32_t)((1ull << x) - 1ull); }       // positions 0 .. x-1, x in [0, 32]
+__device__ __forceinline__ uint32_t half_of(uint64_t mask, int h) { return h ? (uint32_t)(mask >> 32) : (uint32_t)mask; }
+
+template <typename TimeT, int kMode, bool kFill, bool kW>
+__device__ __forceinline__ bool db2_mid_pair(int64_t node0, int64_t n, int64_t delta_i, double delta_f, const Db2Mid& a) {
+    using W = Window<TimeT, kMode>;
+    constexpr int kHalf = kWave / 2;
+    if (node0 + 1 >= n) return false;
+    const int l = lane_id(), h = l >> 5, ll = l & (kHalf - 1), hb = h << 5;
+    const int64_t node = node0 + h, gn = a.lo + node;
+    const uint32_t gnode = (uint32_t)gn;
+    const uint32_t p0 = a.tp[gn], p1 = a.tp[gn + 1], q0 = a.hp[gn], q1 = a.hp[gn + 1];
+    const int32_t row0 = a.row_ptr[node];
+    float d1 = 0.0f, lw1n = 1.0f;
+    int32_t fp = 0;
+    bool simple = true;
+    if (kFill) {
+        d1 = inv_sqrt_deg(a.fo_deg[gn]);
+        lw1n = a.fo_lw[node];
+        fp = a.fo_fwd_ptr[node];
+        simple = a.node_simple[node] != 0;
+    }
+    if (__ballot(p1 - p0 > (uint32_t)kHalf || q1 - q0 > (uint32_t)kHalf || !simple) != 0ull) return false;
+    const int no = (int)(p1 - p0), ni = (int)(q1 - q0);
+    const int nim = max(rl_i(ni, 0), rl_i(ni, kHalf));             // (the loops over in-events: wave-uniform trip count)
+    const bool lo_ = ll < no, li = ll < ni;
+    const TimeT tj = time_of<TimeT>(lo_ ? a.ot_s[p0 + ll] : 0ull);
+    const int cr = lo_ ? (int)a.ocr_s[p0 + ll] : 255;
+    const int32_t rid = (lo_ && a.perm) ? a.perm[row0 + ll] : row0 + ll;
+    const uint32_t q = q0 + ll;
+    uint64_t sti;
+    uint32_t sa, su;
+    float swi;
+    if (!kFill && a.hl != nullptr) {
+        const uint32_t e = li ? a.hl[q] : 0u;
+        Db2Src r;
+        r.t = 0ull; r.u = 0xFFFFFFFFu; r.a = 0xFFFFFFFFu;
+        if (li) r = a.src_t[e];
+        sti = r.t;
+        sa = r.a;
+        su = r.u;
+        swi = (kW && li) ? a.ow_t[e] : 1.0f;
+        if (li) {
+            a.is_t_out[q] = r.t;
+            a.is_a_out[q] = r.a;
+            a.is_u_out[q] = r.u;
+            if (kW) a.is_w_out[q] = swi;
+        }
+    } else {
+        sti = li ? a.is_t[q] : 0ull;
+        sa = li ? a.is_a[q] : 0xFFFFFFFFu;
+        su = li ? a.is_u[q] : 0xFFFFFFFFu;
+        swi = (kW && li) ? a.is_w[q] : 1.0f;
+    }
+    // ---- out side: positions in (successor, time) order
+    const int prevcr = __shfl_up(cr, 1, kWave);
+    const bool ohead = lo_ && (ll == 0 || cr != prevcr);
+    const uint64_t ohm2 = __ballot(ohead);
+    const uint32_t ohm = half_of(ohm2, h);
+    const uint32_t olater = ohm & ~half_below(ll + 1);
+    const int oend = olater ? __ffs((int)olater) - 1 : no;
+    const uint32_t myrun = ohead ? (half_below(oend) & ~half_below(ll)) : 0u;
+    const int from = (hb + (ohead ? cr : ll)) << 2;                 // the successor run with rank cr takes its row's values from position cr
+    const uint32_t v = (uint32_t)lane_read_i(from, rid);
+    // ---- in side: positions in (source node, time) order
+    const uint32_t preva = (uint32_t)__shfl_up((int)sa, 1, kWave);
+    const bool ihead = li && (ll == 0 || sa != preva);
+    if (!kFill) {
+        if (__ballot(li && !ihead) != 0ull) return false;          // two in-events from one source
+        // The window loop is what the kernel issues most of, so it keeps off the vector unit what it can: the masks stay 64 bits wide against a run
+        // mask shifted into the lane's half (no per-lane choice of a half), a mask goes to its owner with one lane write per half (no compare and
+        // select), the pair counts are scalar popcounts, and "reached twice" is left to one test after the loop: a head's hits add up to more than
+        // the in-events that reach it.  The next in-event's time is on its way while this one is tested.
+        const uint64_t myrun2 = (uint64_t)myrun << hb;
+        const int sti_lo = (int)(uint32_t)sti, sti_hi = (int)(uint32_t)(sti >> 32);
+        int my_em_i = 0;                                           // position r: successor runs (head positions) in-event r reaches
+        int pairs0 = 0, pairs1 = 0, hsum = 0;
+        const int ni0 = rl_i(ni, 0), ni1 = rl_i(ni, kHalf);
+        const uint64_t lom = __ballot(lo_);
+        int fz = hb << 2;
+        int nlo = lane_read_i(fz, sti_lo), nhi = lane_read_i(fz, sti_hi);
+        for (int z = 0; z < nim; ++z) {
+            const TimeT ti = time_of<TimeT>(((uint64_t)(uint32_t)nhi << 32) | (uint64_t)(uint32_t)nlo);
+            fz += 4;                                               // (the last one reads a lane of the other half or lane 0: never used)
+            nlo = lane_read_i(fz, sti_lo);
+            nhi = lane_read_i(fz, sti_hi);
+            const typename W::Thr thr = W::threshold(ti, delta_i, delta_f);
+            // one ballot per comparison and scalar ANDs: a ballot of the combined predicate goes through a 0/1 register and a second comparison
+            const uint64_t live = lom & ((z < ni0 ? 0xFFFFFFFFull : 0ull) | (z < ni1 ? 0xFFFFFFFF00000000ull : 0ull));
+            const uint64_t win = __builtin_amdgcn_ballot_w64(tj > ti) & __builtin_amdgcn_ballot_w64(W::admits(tj, thr)) & live;
+            pairs0 += (int)__popc((uint32_t)win);
+            pairs1 += (int)__popc((uint32_t)(win >> 32));
+            const uint64_t hit = win & myrun2;
+            hsum = (int)__popc((uint32_t)(hit >> 32)) + ((int)__popc((uint32_t)hit) + hsum);
+            const uint64_t reach = __builtin_amdgcn_ballot_w64(hit != 0ull);
+            my_em_i = wl_i((int)(uint32_t)reach, z, my_em_i);
+            my_em_i = wl_i((int)(uint32_t)(reach >> 32), kHalf + z, my_em_i);
+        }
+        const uint32_t my_em = (uint32_t)my_em_i;
+        const int all_pairs = h ? pairs1 : pairs0;
+        int col_i = 0;                                             // head position c: the in-events that reach successor run c
+        for (uint32_t hm = (uint32_t)ohm2 | (uint32_t)(ohm2 >> 32); hm != 0u; hm &= hm - 1u) {
+            const int c = __ffs((int)hm) - 1;                      // (a head position of either half: the other half's lanes vote 0, my_em holds head positions only)
+            const uint64_t reach = __builtin_amdgcn_ballot_w64(((my_em >> c) & 1u) != 0u);
+            col_i = wl_i((int)(uint32_t)reach, c, col_i);
+            col_i = wl_i((int)(uint32_t)(reach >> 32), kHalf + c, col_i);
+        }
+        const uint32_t col = (uint32_t)col_i;
+        if (__ballot(ohead && hsum != (int)__popc(col)) != 0ull) return false;      // a successor run reached twice by one in-event
+        if (li) {
+            const int od = (int)__popc(my_em);
+            if (od != 0 && su != 0xFFFFFFFFu) a.outdeg2[su] = od;
+            a.run_em[q] = (uint64_t)my_em;
+        }
+        float deg = 0.0f, lw = -1.0f, deg1 = 0.0f, lw1 = -1.0f;
+        const int su_i = (int)su;
+        for (uint32_t left = ohead ? col : 0u; __ballot(left != 0u) != 0ull;) {
+            const bool act = left != 0u;
+            const int r = act ? __ffs((int)left) - 1 : 0;
+            const uint32_t ur = (uint32_t)lane_read_i((hb + r) << 2, su_i);
+            const float wr = kW ? lane_read_f((hb + r) << 2, swi) : 1.0f;
+            if (act) {
+                if (ur == v) lw = wr; else deg += wr;
+                left &= left - 1u;
+            }
+        }
+        if (ohead) {
+            const float l2 = lw < 0.0f ? 1.0f : lw;
+            a.indeg2[v] = (int)__popc(col);
+            a.ho_deg[v] = deg + l2;
+            a.ho_lw[v] = l2;
+        }
+        // the node's first-order in-edges, one per in-event, summed in their order
+        if (kW) {
+            const int sa_i = (int)sa;
+            for (int z = 0; z < nim; ++z) {
+                const float wz = lane_read_f((hb + z) << 2, swi);
+                const uint32_t az = (uint32_t)lane_read_i((hb + z) << 2, sa_i);
+                if (z < ni) {
+                    if (az == gnode) lw1 = wz; else deg1 += wz;
+                }
+            }
+        } else {
+            // unit weights: a sum of at most 32 ones is their count, and a self loop weighs what a missing one is given
+            const uint32_t selfm = half_of(__ballot(li && sa == gnode), h);
+            deg1 = (float)(ni - (int)__popc(selfm));
+            lw1 = selfm ? 1.0f : -1.0f;
+        }
+        if (ll == 0) {
+            const float l1 = lw1 < 0.0f ? 1.0f : lw1;
+            a.node_simple[node] = 1;
+            a.nu[node] = ni;
+            a.pc[node] = all_pairs;
+            a.fo_deg[gnode] = deg1 + l1;
+            a.fo_lw[node] = l1;
+        }
+        return true;
+    }
+    // ---- fill pass, both nodes simple: all in-runs of both at once (position r = in-event r = in-run r)
+    const uint32_t em = li ? (uint32_t)a.run_em[q] : 0u;
+    const bool ok = li && su < kDb2Foreign;
+    const uint2 rp = ok ? a.row_pack[su] : make_uint2(0u, 0u);
+    const float du = __uint_as_float(rp.x);
+    const int32_t ob = (int32_t)rp.y;
+    const float da = ok ? inv_sqrt_deg(a.fo_deg[sa]) : 0.0f;
+    if (a.fo_bwd_val != nullptr && ohead) {
+        const uint32_t u = (uint32_t)row0 + (uint32_t)cr;
+        const uint32_t c = a.oc_s[p0 + ll];
+        a.fo_bwd_val[u] = gnode == c ? 0.0f : d1 * a.fo_w[u] * inv_sqrt_deg(a.fo_deg[c]);
+    }
+    const float rdeg = lo_ ? a.ho_deg[rid] : 1.0f;
+    const float rlw = lo_ ? a.ho_lw[rid] : 1.0f;
+    const int32_t rip = lo_ ? a.ho_fwd_ptr[rid] : 0;
+    const float dv = inv_sqrt_deg(lane_read_f(from, rdeg));
+    const float lwv = lane_read_f(from, rlw);
+    const int32_t ip = lane_read_i(from, rip);
+    int col_i = 0;
+    for (uint32_t hm = (uint32_t)ohm2 | (uint32_t)(ohm2 >> 32); hm != 0u; hm &= hm - 1u) {
+        const int c = __ffs((int)hm) - 1;
+        const uint64_t reach = __builtin_amdgcn_ballot_w64(((em >> c) & 1u) != 0u);
+        col_i = wl_i((int)(uint32_t)reach, c, col_i);
+        col_i = wl_i((int)(uint32_t)(reach >> 32), kHalf + c, col_i);
+    }
+    const uint32_t col = (uint32_t)col_i;
+    if (li) {
+        uint32_t run_a = sa;
+        if (a.part) run_a = (int64_t)sa < a.lo ? (uint32_t)(a.n_own + sa) : ((int64_t)sa >= a.lo + a.n_own ? sa : (uint32_t)(sa - a.lo));
+        const float w1 = kW ? swi : 1.0f;
+        a.fwd_idx1[fp + ll] = (int32_t)run_a;
+        a.fwd_val1[fp + ll] = sa == gnode ? 0.0f : da * w1 * d1;
+        if (a.dst_order) a.dst_order[fp + ll] = (int32_t)su;
+    }
+    for (uint32_t left = em; __ballot(left != 0u) != 0ull;) {
+        const bool act = left != 0u;
+        const int c = act ? __ffs((int)left) - 1 : 0;
+        const int fc = (hb + c) << 2;
+        const uint32_t vc = (uint32_t)lane_read_i(fc, (int)v);
+        const float dvc = lane_read_f(fc, dv);
+        const int32_t ipc = lane_read_i(fc, ip);
+        const uint32_t reach = (uint32_t)lane_read_i(fc, (int)col);
+        if (act) {
+            const int pos = (int)__popc(reach & half_below(ll));
+            const int rank = (int)__popc(em & half_below(c));
+            const float wgt = kW ? swi : 1.0f;
+            const float val = su == vc ? 0.0f : du * wgt * dvc;
+            a.in_idx2[ipc + pos] = (int32_t)su;
+            a.in_val2[ipc + pos] = val;
+            if (a.in_w2) a.in_w2[ipc + pos] = wgt;
+            a.out_pack[ob + rank] = make_uint2(vc, __float_as_uint(val));
+            left &= left - 1u;
+        }
+    }
+    if (ohead) a.self2[v] = dv * lwv * dv;
+    if (ll == 0 && a.self1) a.self1[node] = d1 * lw1n * d1;
+    return true;
+}
+
+#ifdef PP_DB2_MID_PAIR_PROBE
+// probe builds only: waves of k_db2_mid that {count paired, count one by one, fill paired, fill one by one}, read by pp_debruijn2_pair_probe
+__device__ unsigned long long g_db2_pair_probe[4];
+#endif
+
+// The paired kernel holds both routes and the compiler takes 106 scalar registers for it: 7 waves per SIMD.  Held to 8 waves it parks 40-70 of them
+// in lanes of a vector register outside the loops; measured on the headline stream the count pass goes from 476 to 421 us, the fill pass stays.
+#if PP_DB2_MID_PAIR && !defined(PP_DB2_MID_WAVES)
+#define PP_DB2_MID_WAVES 8
+#endif
+#ifdef PP_DB2_MID_WAVES
+#define PP_DB2_MID_ATTR __attribute__((amdgpu_waves_per_eu(PP_DB2_MID_WAVES, PP_DB2_MID_WAVES)))
+#else
+#define PP_DB2_MID_ATTR
+#endif
+
+template <typename TimeT, int kMode, bool kFill, bool kW>
+__global__ __launch_bounds__(kBlock) PP_DB2_MID_ATTR void k_db2_mid(int64_t n, int64_t delta_i, double delta_f, Db2Mid a) {
+    const int64_t node0 = ((int64_t)blockIdx.x * kWavesPerBlock + wave_id()) * kDb2MidPerWave;
+    if (node0 >= n) return;
+#if PP_DB2_MID_PAIR
+    const bool paired = db2_mid_pair<TimeT, kMode, kFill, kW>(node0, n, delta_i, delta_f, a);
+#ifdef PP_DB2_MID_PAIR_PROBE
+    if (lane_id() == 0) atomicAdd(&g_db2_pair_probe[(kFill ? 2 : 0) + (paired ? 0 : 1)], 1ull);
+#endif
+    if (paired) return;
+#pragma nounroll
+    for (int s = 0; s < kDb2MidPerWave && node0 + s < n; ++s) db2_mid_seq<TimeT, kMode, kFill, kW, 1>(node0 + s, n, delta_i, delta_f, a);      // (one body: the registers of one node)
+#else
+    db2_mid_seq<TimeT, kMode, kFill, kW, kDb2Nodes>(node0, n, delta_i, delta_f, a);
+#endif
 }
 
 // ------------------------------------------------------------------ hub nodes (round 5)
@@ -2037,7 +2302,7 @@ static int db2_count(const char* who, int time_dtype, int64_t m, int64_t n, cons
                hs.tasks <= db2_task_cap(m, n) && hs.parts >= hs.tasks && (hs.hubs == 0 || !part), PP_ERR_ARG, "%s: bad hub sizes", who);
     Db2HubWs hw = carve_db2_hub(hs.hubs > 0 ? hub_ws : nullptr, hs.out_events, hs.out_hubs, hs.parts);
     PP_REQUIRE(hs.hubs == 0 || (hub_ws != nullptr && hub_ws_bytes >= hw.total_bytes), PP_ERR_WORKSPACE, "%s: hub workspace too small", who);
-    const unsigned egrid = (unsigned)ceil_div(m, kBlock), ngrid = (unsigned)ceil_div(n_own > 0 ? n_own : 1, kWavesPerBlock * kDb2Nodes);
+    const unsigned egrid = (unsigned)ceil_div(m, kBlock), ngrid = (unsigned)ceil_div(n_own > 0 ? n_own : 1, kWavesPerBlock * kDb2MidPerWave);
     const int key_bits = bits_for((uint64_t)(n > 0 ? n - 1 : 0));
     int rc;
     if (hs.hubs > 0) {
@@ -2195,7 +2460,7 @@ static int db2_fill(const char* who, int time_dtype, int64_t m, int64_t n, int64
     PP_REQUIRE(m > 0, PP_ERR_ARG, "%s: an empty stream has no order-2 model to fill (use pp_gcn_plan on the empty graph)", who);
     Db2HubWs hw = carve_db2_hub(hs.hubs > 0 ? hub_ws : nullptr, hs.out_events, hs.out_hubs, hs.parts);
     PP_REQUIRE(hs.hubs == 0 || (!part && hub_ws != nullptr && hub_ws_bytes >= hw.total_bytes), PP_ERR_WORKSPACE, "%s: hub workspace too small", who);
-    const unsigned egrid = (unsigned)ceil_div(m, kBlock), ngrid = (unsigned)ceil_div(n_own, kWavesPerBlock * kDb2Nodes);
+    const unsigned egrid = (unsigned)ceil_div(m, kBlock), ngrid = (unsigned)ceil_div(n_own, kWavesPerBlock * kDb2MidPerWave);
     PP_REQUIRE(num_ho_edges >= 0 && (num_ho_edges == 0 || pair_scratch != nullptr), PP_ERR_ARG, "%s: pair_scratch (8 bytes per order-2 edge) missing", who);
     if (!rows_packed) {                          // (one GPU: the count call queued it behind its size copy)
         k_db2_pack_rows<<<egrid, kBlock, 0, st>>>(m, ho_deg, ho_bwd_ptr, w.row_pack);
@@ -2327,5 +2592,19 @@ int pp_debruijn2_part_fill(int time_dtype, int64_t m, int64_t num_nodes, int64_t
                     fo_fwd_val, nullptr, fo_shard_bwd_ptr, fo_shard_bwd_idx, fo_shard_bwd_val, fo_self, nullptr, pair_scratch, ws, ws_bytes, none, nullptr, 0,
                     false, (hipStream_t)stream);
 }
+
+#ifdef PP_DB2_MID_PAIR_PROBE
+// probe builds only (not in the header): the four wave counters of k_db2_mid since the last reset
+int pp_debruijn2_pair_probe(unsigned long long* out4, int reset) {
+    using namespace pp;
+    PP_HIP(hipDeviceSynchronize());
+    PP_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_db2_pair_probe), 4 * sizeof(unsigned long long)));
+    if (reset) {
+        const unsigned long long zero[4] = {0, 0, 0, 0};
+        PP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_db2_pair_probe), zero, sizeof(zero)));
+    }
+    return PP_OK;
+}
+#endif
 
 }  // extern "C"
