@@ -1114,6 +1114,30 @@ int pp_rg_ws_offenders(const int64_t* key, const int32_t* edge, int64_t count, i
 int pp_rg_ws_redraw(int64_t n, int64_t count, int64_t seed, int64_t round, int undirected, const int32_t* flag, int64_t* rows, int64_t* cols,
                     pp_stream_t stream);
 
+/* Degree-sequence models (molloy_reed, k_regular_random, is_graphic_erdos_gallai of the reference's generative_models.py); DESIGN.md
+ * "Degree-sequence models" has the rules.  S = the sum of the n degrees (S < 2^31 - 1, n < 2^31 - 1), M = S / 2 edges, stored as (min, max).
+ *   pp_rg_mr_stubs: ptr [n + 1] the exclusive scan of the degrees (ptr[n] == stubs); node[s] = the node whose range of ptr holds stub s (int32,
+ *   by bisection), key[s] = the word of (PP_RG_TAG_MR_SHUFFLE, stream 0, index s), all 64 bits (int64 with the uint64's bits).
+ *   pp_rg_mr_pair: order [2 edges] = the stubs in the stable unsigned order of their keys; edge i joins node[order[2 i]] and node[order[2 i + 1]].
+ *   pp_rg_mr_claim: claim [edges] uint32 is set to "none" (0xFFFFFFFF), then every flagged edge e draws its victim v_e below `edges` for
+ *   (PP_RG_TAG_MR_VICTIM, round, e) and claim[v_e] = min(claim[v_e], e) (atomic; the result does not depend on the order).
+ *   pp_rg_mr_swap (after pp_rg_mr_claim on the same stream, same arguments): a flagged e with v_e != e, claim[v_e] == e and claim[e] none
+ *   proposes, with (a, b) = edge e and (c, d) = edge v_e — c and d exchanged when bit 0 of the word of (PP_RG_TAG_MR_SIDE, stream round << 32,
+ *   e) is set — e' = (a, c), f' = (b, d), sorted.  bad(x) = x is a loop or (unless multi) x's key is in sorted_key [edges], the ascending keys
+ *   row n + col the flags were made from.  Both edges are rewritten iff bad(e') + (bad(f') || (!multi && f' == e')) <= 1 + flag[v_e].
+ *   pp_rg_eg_check: asc [n] the degrees in ASCENDING order, all in 0 .. n - 1, scan [n + 1] its exclusive scan, so that the descending
+ *   sequence is d_i = asc[n - i] and its prefix sums are P_r = scan[n] - scan[n - r].  violated[0] (int32, zeroed by the call) becomes 1 when
+ *   P_n is odd or P_r > r (r - 1) + r (c_r - r) + P_n - P_{c_r}, c_r = max(r, #{i : d_i > r}), for some r in 1 .. n. */
+#define PP_RG_TAG_MR_SHUFFLE 6
+#define PP_RG_TAG_MR_VICTIM 7
+#define PP_RG_TAG_MR_SIDE 8
+int pp_rg_mr_stubs(const int64_t* ptr, int64_t n, int64_t stubs, int64_t seed, int32_t* node, int64_t* key, pp_stream_t stream);
+int pp_rg_mr_pair(const int32_t* node, const int32_t* order, int64_t edges, int64_t n, int64_t* rows, int64_t* cols, pp_stream_t stream);
+int pp_rg_mr_claim(const int32_t* flag, int64_t edges, int64_t seed, int64_t round, uint32_t* claim, pp_stream_t stream);
+int pp_rg_mr_swap(const int32_t* flag, const uint32_t* claim, const int64_t* sorted_key, int64_t edges, int64_t n, int64_t seed, int64_t round,
+                  int multi, int64_t* rows, int64_t* cols, pp_stream_t stream);
+int pp_rg_eg_check(const int64_t* asc, const int64_t* scan, int64_t n, int32_t* violated, pp_stream_t stream);
+
 /* ------------------------------------------------------------------ power-iteration centralities (pp_graph_power.hip) */
 /* eigenvector_centrality and katz_centrality as networkx 3.4 iterates them (the reference forwards both names to networkx on a DiGraph copy,
  * src/pathpyG/algorithms/centrality.py:327-356), on the PREDECESSOR lists of the distinct edges: col_ptr [n + 1], row [k] int64 (device),

@@ -220,6 +220,43 @@ def random_ring(n: int, s: int, seed: int, threshold: int, always: bool, undirec
     return edge_index
 
 
+def random_degrees(degrees, device=None):
+    """An int64 degree vector on the compute device (a CPU-resident one is staged, like ``z`` of the block model)."""
+    dev = degrees.device if degrees.is_cuda else random_device(device)
+    (degrees,) = _stage(dev, degrees)
+    return degrees.to(torch.int64).contiguous()
+
+
+def random_graphic(degrees) -> bool:
+    """The Erdös-Gallai test of an int64 degree vector on the compute device: the range from ``minmax`` (a degree is in 0 .. n - 1), parity
+    and the condition for r = 1 .. n from ``k_eg_check``."""
+    n = degrees.numel()
+    if n == 0:
+        return True
+    lo, hi = _hip.minmax(degrees)
+    if lo < 0 or hi > n - 1:
+        return False
+    return _hip.rg_eg_check(degrees)
+
+
+def random_matching(degrees, n: int, seed: int, multi: bool, relax: bool, max_rounds: int):
+    """``(edges, rounds)`` of the Molloy-Reed sampler: int64 ``[2, S / 2]`` on the device of ``degrees`` (unsorted, ends sorted) after as many
+    repair rounds as it takes (one read-back per round; none with ``relax``), or ``(None, 0)`` for S = 0."""
+    ptr = _hip.exclusive_scan(degrees)
+    stubs = int(ptr[-1].item())
+    if stubs >= 0x7fffffff:
+        raise ValueError(f"molloy_reed: the degrees sum to {stubs}, 2^31 - 1 or more (stub and edge indices are int32 in the sort)")
+    if stubs == 0:
+        return None, 0
+    edge_index = _hip.rg_mr_matching(ptr, n, stubs, seed)
+    if relax:
+        return edge_index, 0
+    for rnd in range(1, max_rounds + 1):
+        if _hip.rg_mr_repair(edge_index, n, seed, rnd, multi) == 0:
+            return edge_index, rnd - 1
+    raise RuntimeError(f"molloy_reed: edges are still to be repaired after {max_rounds} rounds")
+
+
 def count_unordered(edge_index) -> int:
     if edge_index.size(1) < 2:
         return 0

@@ -2848,3 +2848,53 @@ def rg_ws_repair(edge_index: torch.Tensor, n: int, seed: int, round: int, dups: 
             check(L.pp_rg_ws_redraw(n, k, _i64(seed), round, int(undirected), _p(flag), edge_index[0].data_ptr(), edge_index[1].data_ptr(), _stream()),
                   "pp_rg_ws_redraw")
     return offenders
+
+
+# degree-sequence models: the header's "Degree-sequence models" block, DESIGN.md for the rules
+RG_TAG_MR_SHUFFLE, RG_TAG_MR_VICTIM, RG_TAG_MR_SIDE = 6, 7, 8
+
+
+def rg_eg_check(degrees: torch.Tensor) -> bool:
+    """Whether the int64 degrees, ALL IN ``0 .. n - 1``, meet the Erdös-Gallai condition for r = 1 .. n and have an even sum (one read-back)."""
+    dev = require_device(degrees)
+    n = degrees.numel()
+    asc = sort_pairs(degrees, None, 0, max((n - 1).bit_length(), 1))[0] if n > 1 else degrees.contiguous()
+    scan = exclusive_scan(asc)
+    with torch.cuda.device(dev):
+        violated = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib().pp_rg_eg_check(_p(asc), _p(scan), n, _p(violated), _stream()), "pp_rg_eg_check")
+        return int(violated.item()) == 0
+
+
+def rg_mr_matching(ptr: torch.Tensor, n: int, stubs: int, seed: int) -> torch.Tensor:
+    """The first matching, int64 ``[2, stubs / 2]`` with sorted ends: the stubs of ``ptr`` (the exclusive scan of n degrees, ``ptr[n] == stubs``,
+    even) in the stable order of their 64-bit shuffle keys, neighbours joined."""
+    dev = require_device(ptr)
+    with torch.cuda.device(dev):
+        node = torch.empty(stubs, dtype=torch.int32, device=dev)
+        key = torch.empty(stubs, dtype=torch.int64, device=dev)
+        check(lib().pp_rg_mr_stubs(_p(ptr), n, stubs, _i64(seed), _p(node), _p(key), _stream()), "pp_rg_mr_stubs")
+        _, order = sort_pairs(key, None, 0, 64)
+        out = torch.empty((2, stubs // 2), dtype=torch.int64, device=dev)
+        check(lib().pp_rg_mr_pair(_p(node), _p(order), stubs // 2, n, out[0].data_ptr(), out[1].data_ptr() if stubs // 2 else out.data_ptr(), _stream()),
+              "pp_rg_mr_pair")
+    return out
+
+
+def rg_mr_repair(edge_index: torch.Tensor, n: int, seed: int, round: int, multi: bool) -> int:
+    """One repair round in place: loops and (unless ``multi``) surplus copies claim a victim edge each and exchange ends with it where that
+    makes nothing worse.  Returns the number of offenders it found (0: nothing was changed).  One read-back."""
+    dev = require_device(edge_index)
+    k = edge_index.size(1)
+    sorted_k, order = rg_sorted_keys(edge_index, n)
+    L = lib()
+    with torch.cuda.device(dev):
+        flag = torch.empty(k, dtype=torch.int32, device=dev)
+        check(L.pp_rg_ws_offenders(_p(sorted_k), _p(order), k, n, int(not multi), 1, _p(flag), _stream()), "pp_rg_ws_offenders")
+        offenders = int(exclusive_scan(flag)[-1].item())
+        if offenders:
+            claim = torch.empty(k, dtype=torch.int32, device=dev)                  # (uint32 on the device)
+            check(L.pp_rg_mr_claim(_p(flag), k, _i64(seed), round, _p(claim), _stream()), "pp_rg_mr_claim")
+            check(L.pp_rg_mr_swap(_p(flag), _p(claim), _p(sorted_k), k, n, _i64(seed), round, int(multi), edge_index[0].data_ptr(),
+                                  edge_index[1].data_ptr(), _stream()), "pp_rg_mr_swap")
+    return offenders

@@ -43,8 +43,28 @@ empty mapping, ``is_undirected()`` False, and — nothing having been made on a 
 ``erdos_renyi_gnp_likelihood`` keeps the reference's exponent ``graph.n`` on ``p`` (the likelihood proper has ``graph.m`` there, as the
 log-likelihood does): it is a quirk of the reference and kept so that results agree.  The three likelihood functions are host arithmetic.
 
-**Next step, not here:** ``is_graphic_erdos_gallai``, ``generate_degree_sequence``, ``molloy_reed``, ``molloy_reed_randomize`` and
-``k_regular_random``.  The reference's stub-matching loop with edge break-up has no obvious parallel form with the same distribution.
+**Degree-sequence models** (``is_graphic_erdos_gallai``, ``generate_degree_sequence``, ``molloy_reed``, ``molloy_reed_randomize``,
+``k_regular_random``).  The reference matches stubs one pair at a time, tests ``(v, w) in edges`` on a Python list and breaks up a random
+edge when a draw fails.  Here all stubs are shuffled at once (a sort by 64-bit keys of the stream) and neighbours are joined; loops and
+surplus copies are then repaired in rounds: every offender draws a victim edge, the smallest offender that drew an edge claims it, an
+offender acts when it holds its claim and nobody drew it, and exchanges one end with its victim if that leaves no more loops and
+duplicates among the two edges than before.  Like everything else here the result is a pure function of ``(seed, arguments)``; DESIGN.md
+("Degree-sequence models") has the rules and tests/cpu_ops_degree_models.py restates them.  Deviations, all deliberate:
+
+* *Distribution:* only the first matching is exactly uniform (over stub matchings).  The repaired result is NOT uniform over the simple
+  graphs of the sequence — neither is the reference's loop — and is not the reference's distribution.
+* *Termination* of the repair rounds is not proven for every graphic sequence; ``MAX_REPAIR_ROUNDS`` rounds end in a ``RuntimeError``.
+* *All n nodes are there*, those of degree 0 included; the reference builds the graph from its edge list and loses them.  (An empty edge
+  set is the empty graph, as everywhere in this module.)  Without ``node_ids`` the IDs are the ints ``0 .. n - 1`` as in the reference,
+  not the ``str`` IDs of the other models.
+* *``node_ids`` of the wrong length* is a ``ValueError``; the reference silently ignores the list.
+* *``relax=True``* is one matching without repair, loops dropped and duplicates merged — what the reference's docstring describes.  The
+  reference's code still breaks up an edge on every loop it draws and appends duplicates to its list.
+* *``multiedge=True``* stores parallel edges and repairs only loops.
+* *A single node of even positive degree* is not graphic (the condition is applied for r = 1 .. n; the reference stops at n - 1, says True
+  and its ``molloy_reed([2])`` never returns).  Degrees that are not finite integers are a ``ValueError``.
+* *``generate_degree_sequence``* draws from a seeded ``numpy.random.default_rng`` and gives up after ``MAX_SEQUENCE_TRIES`` draws.
+* Degrees summing to 2^31 - 1 or more are refused: stub and edge indices are int32 in the sort.
 """
 from __future__ import annotations
 
@@ -68,7 +88,9 @@ FRAC_BITS = 40               # fraction bits of -log2(u) on the device
 C_FRAC_BITS = 32             # fraction bits of the skip constant
 MIN_P = 2.0 ** -30           # the smallest positive probability the region sampler takes
 MAX_REPAIR_ROUNDS = 1 << 16
+MAX_SEQUENCE_TRIES = 1 << 12 # draws of generate_degree_sequence before it gives up
 last_seed = None             # the seed of the most recent sampling call of this module
+last_repair_rounds = 0       # repair rounds of the most recent molloy_reed call (rounds that found offenders; 0 with relax)
 
 RECT, STRICT, DIAG, NO_DIAG = 0, 1, 2, 3      # region kinds (RG_* of _hip, kReg* of the kernels)
 
@@ -367,6 +389,132 @@ def watts_strogatz(n: int, s: int, p: float = 0.0, undirected: bool = True, allo
     if mapping is not None:
         g.mapping = mapping
     return g if device is None else g.to(device)
+
+
+# ------------------------------------------------------------------ degree-sequence models
+def _degree_vector(degrees) -> torch.Tensor:
+    """The int64 vector of a list, numpy array or tensor of degrees, where the input lives.  Floating-point entries must be finite and
+    integral (``ValueError``); magnitudes beyond 2^62 are clamped, which changes no answer (no sequence holding one is graphic)."""
+    t = degrees if isinstance(degrees, torch.Tensor) else torch.as_tensor(_np.asarray(degrees))
+    if t.dim() != 1 or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError("a degree sequence is a vector of integers")
+    if t.is_floating_point():
+        if t.numel() > 0 and not bool(torch.isfinite(t).all()):
+            raise ValueError("a degree sequence holds finite integers (found inf or nan)")
+        if t.numel() > 0 and bool((t != t.round()).any()):
+            raise ValueError("a degree sequence holds integers (found a fractional entry)")
+        t = t.to(torch.float64).clamp(-2.0 ** 62, 2.0 ** 62)
+    return t.to(torch.int64)
+
+
+def is_graphic_erdos_gallai(degrees) -> bool:
+    """Whether a simple undirected graph with these node degrees exists: the condition of Erdös and Gallai (1960) for r = 1 .. n on the
+    descending sequence, an even sum and no negative entry.
+
+    ``degrees`` is a list, numpy array or tensor, on the host or the device; floating-point entries must be finite and integral
+    (``ValueError`` otherwise).  The degrees are sorted on the device and one lane tests each r (``k_eg_check``) — the reference runs
+    two nested Python loops.  ``[]`` is graphic.  Unlike the reference (which stops at r = n - 1) a single node of even positive degree is
+    not: the reference's ``molloy_reed([2])`` never returns.
+    """
+    d = _degree_vector(degrees)
+    if d.numel() == 0:
+        return True
+    return _dispatch.random_graphic(_dispatch.random_degrees(d))
+
+
+def generate_degree_sequence(n: int, distribution, *, seed: int | None = None, **distribution_args) -> _np.ndarray:
+    """A random graphic degree sequence of n entries drawn from a degree distribution (a host function; the test is the device's).
+
+    Args:
+        n: the number of nodes
+        distribution: a dict ``{degree: probability}``, sampled with ``numpy.random.default_rng(seed).choice``, or an object with ``rvs``
+            (a frozen scipy.stats distribution), called with ``random_state=`` that generator; non-integer draws are rounded (``rint``)
+        seed: the seed of the numpy generator; ``None``: fresh entropy
+        **distribution_args: passed on to ``rvs``
+
+    The sequence is redrawn until it is graphic; after :data:`MAX_SEQUENCE_TRIES` failed draws a ``RuntimeError`` is raised (the
+    reference loops forever).  Anything else than a dict or an object with ``rvs`` is a ``NotImplementedError``, as in the reference.
+    """
+    if isinstance(distribution, dict):
+        support = list(distribution)
+        probs = [distribution[k] for k in support]
+
+        def draw(rng):
+            return rng.choice(_np.asarray(support), size=n, p=probs)
+    elif hasattr(distribution, "rvs"):
+        def draw(rng):
+            s = _np.asarray(distribution.rvs(size=n, random_state=rng, **distribution_args))
+            return s if _np.issubdtype(s.dtype, _np.integer) else _np.rint(s)
+    else:
+        raise NotImplementedError()
+    rng = _np.random.default_rng(seed)
+    for _ in range(MAX_SEQUENCE_TRIES):
+        s = draw(rng)
+        if is_graphic_erdos_gallai(s):
+            return s
+    raise RuntimeError(f"generate_degree_sequence: no graphic sequence in {MAX_SEQUENCE_TRIES} draws")
+
+
+def molloy_reed(degree_sequence, multiedge: bool = False, relax: bool = False, node_ids: Optional[list] = None, *,
+                seed: int | None = None, device=None) -> Graph:
+    """A random undirected graph without self-loops whose node i has degree ``degree_sequence[i]`` (the configuration model of Molloy and
+    Reed), sampled on the device.
+
+    Args:
+        degree_sequence: the n node degrees (list, numpy array or tensor, host or device); ``ValueError`` unless graphic
+            (:func:`is_graphic_erdos_gallai`), also with ``multiedge`` or ``relax``, and when they sum to 2^31 - 1 or more
+        multiedge: parallel edges are allowed and stored; only loops are repaired
+        relax: one stub matching without repairs: loops are dropped and parallel edges merged, so the graph may have fewer than
+            ``sum(degree_sequence) / 2`` edges and smaller degrees — what the reference's docstring describes
+        node_ids: the n node IDs; default the ints ``0 .. n - 1``.  Another length is a ``ValueError``
+
+    The stubs are shuffled by sorting 64-bit keys of the stream and neighbours are joined — a uniform perfect matching of the stubs.
+    Loops and surplus copies of an edge are then repaired in rounds of disjoint degree-preserving end swaps with randomly drawn victim
+    edges, accepted where they do not make things worse (module docstring; DESIGN.md "Degree-sequence models"); the number of rounds is
+    kept in :data:`last_repair_rounds`.  **Termination is not proven** for every graphic sequence: after :data:`MAX_REPAIR_ROUNDS` rounds
+    with offenders left a ``RuntimeError`` is raised.  Sparse and heavy-tailed sequences take a handful of rounds; a sequence with a single
+    realisation (a complete graph, a star) takes tens to thousands.
+    """
+    global last_repair_rounds
+    d = _degree_vector(degree_sequence)
+    n = d.numel()
+    if node_ids is not None and len(node_ids) != n:
+        raise ValueError(f"node_ids holds {len(node_ids)} IDs for {n} degrees")
+    seed = _seed(seed)
+    last_repair_rounds = 0
+    if n == 0:
+        return _empty(device)
+    d = _dispatch.random_degrees(d, device)
+    if not _dispatch.random_graphic(d):
+        logger.error("given degree sequence is not graphic")
+        raise ValueError("given degree sequence is not graphic")
+    edge_index, last_repair_rounds = _dispatch.random_matching(d, n, seed, bool(multiedge), bool(relax), MAX_REPAIR_ROUNDS)
+    if edge_index is None:
+        return _empty(device)
+    if relax:
+        edge_index = edge_index[:, edge_index[0] != edge_index[1]]
+    mapping = IndexMap(_np.arange(n) if node_ids is None else list(node_ids))
+    return _finish(edge_index, n, mapping, False, device, row_sorted=False, multi=bool(multiedge) and not relax)
+
+
+def molloy_reed_randomize(graph: Graph, *, seed: int | None = None, device=None) -> Graph:
+    """A randomised realisation of an undirected graph's degree sequence (its in-degrees, which count a stored loop once, as the
+    reference's ``degree(edge_index[1])`` does) with the graph's node IDs.  The degrees never leave the device."""
+    if graph.is_directed():
+        logger.error("molloy_reed_randomize is only implemented for undirected graphs")
+        raise NotImplementedError("molloy_reed_randomize is only implemented for undirected graphs")
+    return molloy_reed(graph.degrees(mode="in", return_tensor=True), node_ids=graph.nodes, seed=seed, device=device)
+
+
+def k_regular_random(k: int, n: Optional[int] = None, node_ids: Optional[list] = None, *, seed: int | None = None, device=None) -> Graph:
+    """A random graph in which every node has degree k: ``molloy_reed([k] * n, node_ids=node_ids)``; ``n`` defaults to ``len(node_ids)``."""
+    if k < 0:
+        raise ValueError("Degree parameter k must be non-negative")
+    if n is None and node_ids is None:
+        raise ValueError("You must either pass a list of node ids or a number of nodes to generate")
+    if n is None:
+        n = len(node_ids)
+    return molloy_reed(torch.full((int(n),), int(k), dtype=torch.int64), multiedge=False, relax=False, node_ids=node_ids, seed=seed, device=device)
 
 
 # ------------------------------------------------------------------ likelihoods (host arithmetic)

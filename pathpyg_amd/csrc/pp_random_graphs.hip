@@ -284,6 +284,95 @@ __global__ __launch_bounds__(kBlock) void k_ws_redraw(int64_t n, int64_t count, 
     }
 }
 
+// ---- degree-sequence models (Molloy-Reed): DESIGN.md "Degree-sequence models" has the rules, tests/cpu_ops_degree_models.py restates them
+constexpr uint32_t kMrNone = 0xFFFFFFFFu;      // claim[f]: no offender drew f
+
+// stub s belongs to the node v with ptr[v] <= s < ptr[v + 1] (ptr[0] == 0, ptr[n] == stubs; a node of degree 0 owns no stub)
+__global__ __launch_bounds__(kBlock) void k_mr_stubs(const int64_t* __restrict__ ptr, int64_t n, int64_t stubs, uint32_t k0, uint32_t k1,
+                                                    int32_t* __restrict__ node, int64_t* __restrict__ key) {
+    for (int64_t s = (int64_t)blockIdx.x * kBlock + threadIdx.x; s < stubs; s += (int64_t)gridDim.x * kBlock) {
+        int64_t lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (ptr[mid] <= s) lo = mid; else hi = mid;
+        }
+        node[s] = (int32_t)lo;
+        key[s] = (int64_t)rg_word(k0, k1, PP_RG_TAG_MR_SHUFFLE, 0, (uint64_t)s);
+    }
+}
+
+// edge i joins the stubs at the sorted positions 2 i and 2 i + 1, ends sorted
+__global__ __launch_bounds__(kBlock) void k_mr_pair(const int32_t* __restrict__ node, const int32_t* __restrict__ order, int64_t edges, int64_t n,
+                                                   int64_t* __restrict__ row, int64_t* __restrict__ col) {
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < edges; i += (int64_t)gridDim.x * kBlock) {
+        const int64_t s0 = order[2 * i], s1 = order[2 * i + 1];
+        int64_t u = (uint64_t)s0 < (uint64_t)(2 * edges) ? node[s0] : 0, w = (uint64_t)s1 < (uint64_t)(2 * edges) ? node[s1] : 0;
+        if ((uint64_t)u >= (uint64_t)n) u = 0;                                          // (an edge never names a node that is not there)
+        if ((uint64_t)w >= (uint64_t)n) w = 0;
+        row[i] = u < w ? u : w;
+        col[i] = u < w ? w : u;
+    }
+}
+
+// claim[f] = the smallest offender whose victim draw is f (a minimum: the order of the atomics does not matter)
+__global__ __launch_bounds__(kBlock) void k_mr_claim(const int32_t* __restrict__ flag, int64_t edges, uint32_t k0, uint32_t k1, uint64_t round,
+                                                    uint32_t* __restrict__ claim) {
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < edges; e += (int64_t)gridDim.x * kBlock) {
+        if (!flag[e]) continue;
+        const uint64_t f = rg_below((uint64_t)edges, k0, k1, PP_RG_TAG_MR_VICTIM, round, (uint64_t)e);            // (a multiply-high: f < edges)
+        atomicMin(&claim[f], (uint32_t)e);
+    }
+}
+
+__device__ __forceinline__ bool mr_present(const int64_t* __restrict__ sorted_key, int64_t count, int64_t key) {
+    int64_t lo = 0, hi = count;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (sorted_key[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo < count && sorted_key[lo] == key;
+}
+
+// An offender e acts iff its victim f is another edge, f is claimed by e and nobody drew e: acting pairs are disjoint (an acting offender is
+// nobody's victim, its victim is its own and does not act), so both edges are read and written with plain accesses.  sorted_key and flag are
+// the round-start snapshot; nothing here reads an edge another lane may write.
+__global__ __launch_bounds__(kBlock) void k_mr_swap(const int32_t* __restrict__ flag, const uint32_t* __restrict__ claim,
+                                                   const int64_t* __restrict__ sorted_key, int64_t edges, int64_t n, uint32_t k0, uint32_t k1,
+                                                   uint64_t round, int multi, int64_t* __restrict__ row, int64_t* __restrict__ col) {
+    for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < edges; e += (int64_t)gridDim.x * kBlock) {
+        if (!flag[e]) continue;
+        const int64_t f = (int64_t)rg_below((uint64_t)edges, k0, k1, PP_RG_TAG_MR_VICTIM, round, (uint64_t)e);   // the draw of k_mr_claim again
+        if (f == e || claim[f] != (uint32_t)e || claim[e] != kMrNone) continue;
+        const int64_t a = row[e], b = col[e];
+        int64_t c = row[f], d = col[f];
+        if (rg_word(k0, k1, PP_RG_TAG_MR_SIDE, round << 32, (uint64_t)e) & 1) { const int64_t x = c; c = d; d = x; }
+        const int64_t e0 = a < c ? a : c, e1 = a < c ? c : a, f0 = b < d ? b : d, f1 = b < d ? d : b;
+        const bool bad_e = e0 == e1 || (!multi && mr_present(sorted_key, edges, e0 * n + e1));
+        const bool bad_f = f0 == f1 || (!multi && (mr_present(sorted_key, edges, f0 * n + f1) || (f0 == e0 && f1 == e1)));
+        if ((int)bad_e + (int)bad_f > 1 + (flag[f] != 0)) continue;                    // worse than before: the proposal is dropped
+        row[e] = e0; col[e] = e1;
+        row[f] = f0; col[f] = f1;
+    }
+}
+
+// Erdös-Gallai, one lane per r = 1 .. n: asc holds the degrees ascending (all in 0 .. n - 1), scan its exclusive scan, so the descending
+// sequence is d_i = asc[n - i] and P_r = scan[n] - scan[n - r].  With c = max(r, #{i : d_i > r}) the condition is
+// P_r <= r (r - 1) + r (c - r) + P_n - P_c; every term stays below 2^62.  Every violating lane stores the same 1.
+__global__ __launch_bounds__(kBlock) void k_eg_check(const int64_t* __restrict__ asc, const int64_t* __restrict__ scan, int64_t n,
+                                                    int32_t* __restrict__ violated) {
+    const int64_t total = scan[n];
+    for (int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x + 1; r <= n; r += (int64_t)gridDim.x * kBlock) {
+        int64_t lo = 0, hi = n;                                                         // the first position of asc with a degree > r
+        while (lo < hi) {
+            const int64_t mid = lo + ((hi - lo) >> 1);
+            if (asc[mid] <= r) lo = mid + 1; else hi = mid;
+        }
+        const int64_t above = n - lo, c = above > r ? above : r;
+        const int64_t lhs = total - scan[n - r], rhs = r * (r - 1) + r * (c - r) + scan[n - c];
+        if (lhs > rhs || (r == 1 && (total & 1))) violated[0] = 1;
+    }
+}
+
 static unsigned rg_grid(int64_t items) {
     int64_t g = ceil_div(items > 0 ? items : 1, kBlock);
     const int64_t share = shared_grid(kMaxGrid);
@@ -414,6 +503,63 @@ int pp_rg_ws_redraw(int64_t n, int64_t count, int64_t seed, int64_t round, int u
     if (count == 0) return PP_OK;
     k_ws_redraw<<<rg_grid(count), kBlock, 0, (hipStream_t)stream>>>(n, count, (uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint64_t)round, undirected, flag,
                                                                    rows, cols);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_rg_mr_stubs(const int64_t* ptr, int64_t n, int64_t stubs, int64_t seed, int32_t* node, int64_t* key, pp_stream_t stream) {
+    using namespace pp;
+    PP_REQUIRE(n >= 0 && stubs >= 0, PP_ERR_ARG, "pp_rg_mr_stubs: bad sizes");
+    PP_REQUIRE(n < (int64_t)0x7fffffff && stubs < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_rg_mr_stubs: 2^31 - 1 nodes or stubs, or more");
+    PP_REQUIRE(stubs == 0 || (n >= 1 && ptr && node && key), PP_ERR_ARG, "pp_rg_mr_stubs: null pointer, or stubs without nodes");
+    if (stubs == 0) return PP_OK;
+    k_mr_stubs<<<rg_grid(stubs), kBlock, 0, (hipStream_t)stream>>>(ptr, n, stubs, (uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), node, key);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_rg_mr_pair(const int32_t* node, const int32_t* order, int64_t edges, int64_t n, int64_t* rows, int64_t* cols, pp_stream_t stream) {
+    using namespace pp;
+    PP_REQUIRE(edges >= 0 && n >= 0, PP_ERR_ARG, "pp_rg_mr_pair: bad sizes");
+    PP_REQUIRE(n < (int64_t)0x7fffffff && 2 * edges < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_rg_mr_pair: 2^31 - 1 nodes or stubs, or more");
+    PP_REQUIRE(edges == 0 || (n >= 1 && node && order && rows && cols), PP_ERR_ARG, "pp_rg_mr_pair: null pointer, or edges without nodes");
+    if (edges == 0) return PP_OK;
+    k_mr_pair<<<rg_grid(edges), kBlock, 0, (hipStream_t)stream>>>(node, order, edges, n, rows, cols);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_rg_mr_claim(const int32_t* flag, int64_t edges, int64_t seed, int64_t round, uint32_t* claim, pp_stream_t stream) {
+    using namespace pp;
+    PP_REQUIRE(edges >= 0 && round >= 0 && round < (1 << 24) && (edges == 0 || (flag && claim)), PP_ERR_ARG, "pp_rg_mr_claim: bad arguments");
+    PP_REQUIRE(edges < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_rg_mr_claim: 2^31 - 1 edges or more");
+    if (edges == 0) return PP_OK;
+    PP_HIP(hipMemsetAsync(claim, 0xFF, (size_t)edges * sizeof(uint32_t), (hipStream_t)stream));                      // kMrNone in every word
+    k_mr_claim<<<rg_grid(edges), kBlock, 0, (hipStream_t)stream>>>(flag, edges, (uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), (uint64_t)round, claim);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_rg_mr_swap(const int32_t* flag, const uint32_t* claim, const int64_t* sorted_key, int64_t edges, int64_t n, int64_t seed, int64_t round,
+                  int multi, int64_t* rows, int64_t* cols, pp_stream_t stream) {
+    using namespace pp;
+    PP_REQUIRE(edges >= 0 && n >= 1 && round >= 0 && round < (1 << 24), PP_ERR_ARG, "pp_rg_mr_swap: bad arguments");
+    PP_REQUIRE(n < (int64_t)0x7fffffff && edges < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_rg_mr_swap: 2^31 - 1 nodes or edges, or more");
+    PP_REQUIRE(edges == 0 || (flag && claim && sorted_key && rows && cols), PP_ERR_ARG, "pp_rg_mr_swap: null pointer");
+    if (edges == 0) return PP_OK;
+    k_mr_swap<<<rg_grid(edges), kBlock, 0, (hipStream_t)stream>>>(flag, claim, sorted_key, edges, n, (uint32_t)seed, (uint32_t)((uint64_t)seed >> 32),
+                                                                 (uint64_t)round, multi, rows, cols);
+    PP_LAUNCH_CHECK();
+    return PP_OK;
+}
+
+int pp_rg_eg_check(const int64_t* asc, const int64_t* scan, int64_t n, int32_t* violated, pp_stream_t stream) {
+    using namespace pp;
+    PP_REQUIRE(n >= 0 && violated && (n == 0 || (asc && scan)), PP_ERR_ARG, "pp_rg_eg_check: bad arguments");
+    PP_REQUIRE(n < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_rg_eg_check: 2^31 - 1 degrees or more");
+    PP_HIP(hipMemsetAsync(violated, 0, sizeof(int32_t), (hipStream_t)stream));
+    if (n == 0) return PP_OK;
+    k_eg_check<<<rg_grid(n), kBlock, 0, (hipStream_t)stream>>>(asc, scan, n, violated);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
