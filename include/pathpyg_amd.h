@@ -1168,6 +1168,63 @@ int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const dou
                            int64_t batch, int group, int64_t heavy_min, double* values, int64_t* iterations, int64_t* converged, int64_t* grids,
                            void* ws, size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ node layouts (pp_graph_layout.hip) */
+/* The layouts of the reference's visualisations/layout.py:69-269 that are arithmetic: Fruchterman-Reingold as networkx 3.4's dense routine
+ * iterates it (the reference hands "spring" to networkx.spring_layout), random, circular, grid.  Positions are [n, 2] row-major on the
+ * device, float64 except where stated.  n < 2^31 - 1, entries < 2^31 - 1, else PP_ERR_TOO_LARGE before any launch.
+ *
+ * Adjacency (what the reference gets from to_scipy_sparse_matrix -> from_scipy_sparse_array -> nx.Graph): symmetric, one entry per unordered
+ * pair {u, v}, u != v, with a stored edge in either direction; its value is 1 (weight == NULL) or the weight [m] (float64) of the LAST such
+ * edge in the stored order of edge_index [2, m] (int64).  Self-loops and edges with an end outside [0, n) give no entry.  CSR sorted by (row,
+ * neighbour): ptr [n + 1], nbr [nnz] int64, w [nnz] float64.  pp_graph_layout_adj_count sorts the 2 m directed copies stably, flags the last
+ * of every run and leaves nnz in the HOST word `nnz` (one synchronisation; needs 2 m < 2^31 - 1); pp_graph_layout_adj_fill, on the same
+ * stream with the same workspace untouched in between, writes the three arrays.  ws: pp_graph_layout_adj_ws_bytes(m).
+ *
+ * pp_graph_layout_iterate: from pos (read, then overwritten with the result), at most `iterations` times
+ *     disp_i = sum_j (p_i - p_j) (k^2 / max(d_ij, 0.01)^2 - A_ij max(d_ij, 0.01) / k);  len_i = |disp_i|, 0.1 where that is < 0.01;
+ *     dp_i = disp_i (t / len_i), 0 where fixed[i] (uint8 [n] or NULL);  p_i += dp_i;  t -= dt;  stop if sqrt(sum |dp_i|^2) / n < threshold
+ * (false for a NaN).  auto_t: t = 0.1 max(extent x, extent y) of pos and dt = t / (iterations + 1) are computed on the device, the
+ * arguments t and dt are not read.  iterations_run, last_err (the last value of sqrt(sum |dp|^2) / n), grids [4] are HOST words; grids =
+ * {target blocks, source chunks, workgroups of the light attraction launch, of the heavy one}.
+ * Launch scheme: one iteration is 3 plain launches, 4 with heavy nodes (all-pairs repulsion; attraction over the CSR fused with the update;
+ * [the same for heavy nodes]; decide).  No cooperative launch, no grid-wide barrier, no floating-point atomics.  Every kernel reads the
+ * device's `done` word first and does nothing once it is set.  The host enqueues `batch` iterations (0 = 16), synchronises the stream and
+ * reads the state words once per batch.
+ * Summation: repulsion — a workgroup of `block` threads (0 = 256; 64, 128, 256) owns `block` targets and one of `chunks` equal pieces of the
+ * source range (0 = enough for about 2048 workgroups, at most 64 and at most n / 256 rounded up: pp_graph_layout_chunks); a thread adds the
+ * sources of its piece in order into four accumulators (source j of the piece: accumulator j mod 4), folded (0 + 1) + (2 + 3); the pieces of
+ * a node are added in order.  Attraction — `group` lanes per node (a power of two up to 64; 0 = the smallest power of two no less than
+ * nnz / n, between 4 and 64), lane j adding entries j, j + group, ..., folded by a butterfly; a node of heavy_min entries or more (0 =
+ * pp_graph_layout_heavy_min() = 1024) by a whole workgroup, thread j adding entries j, j + 256, ... .  sum |dp|^2: per-workgroup partials
+ * folded by index in a fixed shape.  Every output has the same bits on every run with the same inputs and settings; `batch` never changes a
+ * bit.  ws: pp_graph_layout_ws_bytes(n, block, chunks).
+ *
+ * pp_graph_layout_rescale: networkx.rescale_layout, then + center: p -= mean per axis; p *= scale / max |p| if that is > 0; p += (cx, cy).
+ * pp_graph_layout_start: pos[v] = given[v] where given != NULL and (has == NULL or has[v], uint8), else uniform[0, 1) * dom_size + center,
+ * the uniform being the top 53 bits of the Philox word of (seed, PP_RG_TAG_LAYOUT, stream 0, index 2 v + axis) times 2^-53.
+ * pp_graph_layout_random: float32 [n, 2]: the top 24 bits of the same words times 2^-24, + center in float32.
+ * pp_graph_layout_closed_form: PP_LAYOUT_CIRCULAR: (cos, sin) in float32 of the float32 angle 2 pi v / n, widened; PP_LAYOUT_GRID: with
+ * s = floor(sqrt(n)): (v mod s, -floor(v / s)) / s. */
+#define PP_RG_TAG_LAYOUT 9
+enum { PP_LAYOUT_CIRCULAR = 0, PP_LAYOUT_GRID = 1 };
+int64_t pp_graph_layout_heavy_min(void);
+int64_t pp_graph_layout_chunks(int64_t n, int block, int64_t chunks);
+size_t pp_graph_layout_ws_bytes(int64_t n, int block, int64_t chunks);
+int pp_graph_layout_iterate(const int64_t* ptr, const int64_t* nbr, const double* w, int64_t n, int64_t nnz, double* pos, const uint8_t* fixed,
+                            double k, double t, double dt, int auto_t, int64_t iterations, double threshold, int64_t batch, int block,
+                            int64_t chunks, int group, int64_t heavy_min, int64_t* iterations_run, double* last_err, int64_t* grids, void* ws,
+                            size_t ws_bytes, pp_stream_t stream);
+size_t pp_graph_layout_rescale_ws_bytes(void);
+int pp_graph_layout_rescale(double* pos, int64_t n, double scale, double cx, double cy, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_graph_layout_start(int64_t seed, int64_t n, double dom_size, double cx, double cy, const double* given, const uint8_t* has, double* pos,
+                          pp_stream_t stream);
+int pp_graph_layout_random(int64_t seed, int64_t n, float cx, float cy, float* pos, pp_stream_t stream);
+int pp_graph_layout_closed_form(int kind, int64_t n, double* pos, pp_stream_t stream);
+size_t pp_graph_layout_adj_ws_bytes(int64_t m);
+int pp_graph_layout_adj_count(const int64_t* edge_index, int64_t m, int64_t n, int64_t* nnz, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_graph_layout_adj_fill(const double* weight, int64_t m, int64_t n, int64_t nnz, int64_t* ptr, int64_t* nbr, double* w, void* ws,
+                             size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

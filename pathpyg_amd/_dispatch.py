@@ -155,6 +155,65 @@ def graph_power_centrality(graph, mode: int, threshold: float, max_iter: int, al
     return (values, stats.iterations, stats.converged, stats) if with_stats else (values, stats.iterations, stats.converged)
 
 
+def layout_adjacency(edge_index, weight, num_nodes: int):
+    """``(ptr, nbr, w)`` on the compute device: the symmetric adjacency the reference's layouts see (csrc/pp_graph_layout.hip) — one entry
+    per unordered pair with a stored edge in either direction, valued 1 or, with ``weight`` (one value per stored edge), by the LAST such
+    edge in stored order; self-loops dropped.  CPU-resident inputs are staged."""
+    dev = compute_device(edge_index, weight)
+    ei, weight = _stage(dev, edge_index, weight)
+    return _hip.graph_layout_adjacency(ei, weight, num_nodes)
+
+
+def graph_layout_adjacency(graph, weight=None):
+    """:func:`layout_adjacency` of a Graph; ``weight``: ``None``, the name of an edge attribute or a tensor with one value per stored edge."""
+    if isinstance(weight, str):
+        weight = torch.as_tensor(graph.data[weight])
+    return layout_adjacency(graph.data.edge_index, weight, graph.n)
+
+
+def graph_fr_layout(adjacency, pos, k: float, t, dt, iterations: int, threshold: float, fixed=None, with_stats: bool = False, block: int = 0,
+                    chunks: int = 0, group: int = 0, heavy_min: int = 0, batch: int = 0):
+    """``(pos float64 [n, 2] on the compute device, iterations_run, last_err)`` of the Fruchterman-Reingold iteration (csrc/pp_graph_layout.hip)
+    from ``pos`` over ``adjacency = (ptr, nbr, w)``; with ``with_stats`` the ``_hip.LayoutStats`` follow.  ``t`` and ``dt``: the temperature
+    and its step, or ``t=None`` for networkx's (a tenth of the larger extent of ``pos``, ``t / (iterations + 1)``), computed on the
+    device.  ``fixed``: a bool / uint8 ``[n]`` mask or ``None``.  Kernel settings, 0 = the library's choice: ``block`` (targets per
+    repulsion workgroup: 64, 128, 256), ``chunks`` (pieces of the source range, up to 64), ``group`` (lanes per neighbour list),
+    ``heavy_min`` (list length that gets a whole workgroup), ``batch`` (iterations per read-back; never changes a bit).  CPU-resident
+    inputs are staged."""
+    dev = compute_device(pos, *adjacency)
+    ptr, nbr, w, pos, fixed = _stage(dev, *adjacency, torch.as_tensor(pos), None if fixed is None else torch.as_tensor(fixed))
+    out, ran, err, stats = _hip.graph_layout_iterate(ptr, nbr, w, pos.to(torch.float64), k, t, dt, iterations, threshold, fixed, block, chunks,
+                                                     group, heavy_min, batch)
+    return (out, ran, err, stats) if with_stats else (out, ran, err)
+
+
+def layout_start(seed: int, n: int, dom_size: float, center, given=None, has=None, device=None):
+    """Start positions of the spring layout on the compute device: ``given`` (float64 ``[n, 2]``) where ``has`` (bool ``[n]``; ``None``:
+    everywhere), else Philox draws ``uniform[0, 1) * dom_size + center``."""
+    dev = random_device(device)
+    given, has = _stage(dev, given, has)
+    if given is not None:
+        given = given.to(torch.float64).contiguous()
+    if has is not None:
+        has = has.to(torch.uint8).contiguous()
+    return _hip.graph_layout_start(seed, n, dom_size, center, given, has, dev)
+
+
+def layout_random(seed: int, n: int, center, device=None):
+    return _hip.graph_layout_random(seed, n, center, random_device(device))
+
+
+def layout_closed_form(kind: int, n: int, device=None):
+    return _hip.graph_layout_closed_form(kind, n, random_device(device))
+
+
+def layout_rescale(pos, scale: float, center):
+    return _hip.graph_layout_rescale(pos, scale, center)
+
+
+LAYOUT_CIRCULAR, LAYOUT_GRID = _hip.LAYOUT_CIRCULAR, _hip.LAYOUT_GRID
+
+
 def random_device(device=None) -> torch.device:
     """Where a random graph is sampled: ``device`` if it names a GPU, else the current one (a host ``device`` only receives the result)."""
     if device is not None and torch.device(device).type == "cuda":

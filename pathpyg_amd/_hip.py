@@ -1015,6 +1015,121 @@ def graph_power_iterate(col_ptr: torch.Tensor, row: torch.Tensor, weight: torch.
     return values, PowerStats(int(iterations.value), bool(converged.value), int(grids[0]), int(grids[1]))
 
 
+# ------------------------------------------------------------------ node layouts (pp_graph_layout.hip)
+LAYOUT_CIRCULAR, LAYOUT_GRID = 0, 1
+
+
+def layout_heavy_min() -> int:
+    """The neighbour-list length from which the layout iteration gives a node a whole workgroup (the library's default)."""
+    return int(lib().pp_graph_layout_heavy_min())
+
+
+class LayoutStats(NamedTuple):
+    target_blocks: int      # grid x of the repulsion launch
+    chunks: int             # grid y of the repulsion launch: the pieces of the source range
+    light_grid: int         # workgroups of the light attraction launch
+    heavy_grid: int         # workgroups of the heavy attraction launch (0: no node reached heavy_min)
+
+
+def graph_layout_adjacency(edge_index: torch.Tensor, weight: torch.Tensor | None, num_nodes: int):
+    """``(ptr int64 [n + 1], nbr int64 [nnz], w float64 [nnz])`` on the device: the symmetric adjacency of ``pp_graph_layout_adj_count`` /
+    ``_fill`` in the header (last stored edge of a pair wins, self-loops dropped)."""
+    ei = _edge_index(edge_index)
+    n, m = int(num_nodes), ei.size(1)
+    if weight is not None:
+        if weight.numel() != m:
+            raise ValueError(f"weight must have one value per stored edge ({m}), got {weight.numel()}")
+        weight = weight.reshape(-1).to(torch.float64).contiguous()
+    dev = require_device(ei, weight)
+    L = lib()
+    with torch.cuda.device(dev):
+        nnz = ctypes.c_int64(0)
+        ws = _workspace(L.pp_graph_layout_adj_ws_bytes(m), dev)
+        check(L.pp_graph_layout_adj_count(_p(ei), m, n, ctypes.addressof(nnz), _p(ws), ws.numel(), _stream()), "pp_graph_layout_adj_count")
+        k = int(nnz.value)
+        ptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        nbr = torch.empty(k, dtype=torch.int64, device=dev)
+        w = torch.empty(k, dtype=torch.float64, device=dev)
+        check(L.pp_graph_layout_adj_fill(_p(weight), m, n, k, _p(ptr), _p(nbr), _p(w), _p(ws), ws.numel(), _stream()), "pp_graph_layout_adj_fill")
+    return ptr, nbr, w
+
+
+def graph_layout_iterate(ptr: torch.Tensor, nbr: torch.Tensor, w: torch.Tensor | None, pos: torch.Tensor, k: float, t: float | None,
+                         dt: float | None, iterations: int, threshold: float, fixed: torch.Tensor | None = None, block: int = 0,
+                         chunks: int = 0, group: int = 0, heavy_min: int = 0, batch: int = 0):
+    """Fruchterman-Reingold iterations from ``pos`` (float64 ``[n, 2]``, not modified): ``(new pos, iterations run, last err, LayoutStats)``;
+    see ``pp_graph_layout_iterate`` in the header.  ``t is None``: the temperature and its step come from the extent of ``pos``, on the
+    device.  ``block``, ``chunks``, ``group``, ``heavy_min`` and ``batch``: 0 = the library's choice."""
+    n, nnz = pos.size(0), nbr.numel()
+    if pos.dim() != 2 or pos.size(1) != 2 or pos.dtype != torch.float64:
+        raise ValueError(f"pos must be float64 [n, 2], got {pos.dtype} {tuple(pos.shape)}")
+    if ptr.numel() != n + 1:
+        raise ValueError(f"ptr must have n + 1 = {n + 1} entries, got {ptr.numel()}")
+    ptr, nbr = ptr.to(torch.int64).contiguous(), nbr.to(torch.int64).contiguous()
+    if w is not None:
+        if w.dtype != torch.float64 or w.numel() != nnz:
+            raise ValueError(f"w must be a float64 vector of {nnz} entries")
+        w = w.contiguous()
+    if fixed is not None:
+        if fixed.numel() != n:
+            raise ValueError(f"fixed must have {n} entries")
+        fixed = fixed.reshape(-1).to(torch.uint8).contiguous()
+    dev = require_device(ptr, nbr, w, pos, fixed)
+    L = lib()
+    with torch.cuda.device(dev):
+        out = pos.contiguous().clone()
+        ran, err, grids = ctypes.c_int64(0), ctypes.c_double(0.0), (ctypes.c_int64 * 4)()
+        ws = _workspace(L.pp_graph_layout_ws_bytes(n, int(block), int(chunks)), dev)
+        check(L.pp_graph_layout_iterate(_p(ptr), _p(nbr), _p(w), n, nnz, _p(out), _p(fixed), float(k), 0.0 if t is None else float(t),
+                                        0.0 if dt is None else float(dt), int(t is None), int(iterations), float(threshold), int(batch),
+                                        int(block), int(chunks), int(group), int(heavy_min), ctypes.addressof(ran), ctypes.addressof(err),
+                                        ctypes.addressof(grids), _p(ws), ws.numel(), _stream()), "pp_graph_layout_iterate")
+    return out, int(ran.value), float(err.value), LayoutStats(*(int(g) for g in grids))
+
+
+def graph_layout_rescale(pos: torch.Tensor, scale: float, center) -> torch.Tensor:
+    """``networkx.rescale_layout(pos, scale) + center`` of float64 ``[n, 2]`` positions, in place."""
+    dev = require_device(pos)
+    L = lib()
+    with torch.cuda.device(dev):
+        ws = _workspace(L.pp_graph_layout_rescale_ws_bytes(), dev)
+        check(L.pp_graph_layout_rescale(_p(pos), pos.size(0), float(scale), float(center[0]), float(center[1]), _p(ws), ws.numel(), _stream()),
+              "pp_graph_layout_rescale")
+    return pos
+
+
+def graph_layout_start(seed: int, n: int, dom_size: float, center, given: torch.Tensor | None, has: torch.Tensor | None, device) -> torch.Tensor:
+    """Start positions float64 ``[n, 2]``: ``given`` where ``has`` (or everywhere if ``has is None``), else ``uniform[0, 1) * dom_size + center``."""
+    dev = torch.device(device)
+    L = lib()
+    with torch.cuda.device(dev):
+        pos = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        check(L.pp_graph_layout_start(_i64(seed), n, float(dom_size), float(center[0]),
+                                      float(center[1]), _p(given), _p(has), _p(pos), _stream()), "pp_graph_layout_start")
+    return pos
+
+
+def graph_layout_random(seed: int, n: int, center, device) -> torch.Tensor:
+    """float32 ``[n, 2]`` uniform in ``[0, 1) + center``."""
+    dev = torch.device(device)
+    L = lib()
+    with torch.cuda.device(dev):
+        pos = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        check(L.pp_graph_layout_random(_i64(seed), n, float(center[0]), float(center[1]),
+                                       _p(pos), _stream()), "pp_graph_layout_random")
+    return pos
+
+
+def graph_layout_closed_form(kind: int, n: int, device) -> torch.Tensor:
+    """float64 ``[n, 2]``: the unit circle of ``networkx.circular_layout`` before its rescale, or the reference's grid."""
+    dev = torch.device(device)
+    L = lib()
+    with torch.cuda.device(dev):
+        pos = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        check(L.pp_graph_layout_closed_form(int(kind), n, _p(pos), _stream()), "pp_graph_layout_closed_form")
+    return pos
+
+
 # ------------------------------------------------------------------ DBGNN message passing
 class CsrPlan:
     """CSR pair of one propagation: ``fwd`` rows are the destinations, ``bwd`` rows the sources (transposed)."""

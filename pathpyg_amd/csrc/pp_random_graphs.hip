@@ -18,6 +18,7 @@
 // the fill pass regenerates the streams and stages kRgStage edges per lane in LDS, which the workgroup copies out as full 128-byte runs.
 #include "pp_common.h"
 #include "pp_internal.h"
+#include "pp_philox.h"
 
 namespace pp {
 
@@ -27,18 +28,6 @@ constexpr int kRgRegionWords = 8;      // int64 words of a region descriptor
 constexpr int kRgMaxAttempts = 4096;   // a bounded draw is rejected with probability < 1/2 per attempt
 
 enum { kRegRect = 0, kRegStrict = 1, kRegDiag = 2, kRegNoDiag = 3 };
-
-__device__ __forceinline__ uint64_t rg_word(uint32_t k0, uint32_t k1, uint32_t tag, uint64_t stream, uint64_t index) {
-    uint32_t c0 = (uint32_t)index, c1 = (uint32_t)(index >> 32), c2 = (uint32_t)stream, c3 = (tag << 24) | ((uint32_t)(stream >> 32) & 0xFFFFFFu);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (uint32_t)p1; c2 = n2; c3 = (uint32_t)p0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return (uint64_t)c0 | ((uint64_t)c1 << 32);
-}
 
 // -log2(((w >> 1) + 1) / 2^63) with kRgFrac fraction bits, rounded up by less than 2^-40
 __device__ __forceinline__ uint64_t rg_neglog2(uint64_t w) {
