@@ -25,16 +25,12 @@
 
 #include "pp_common.h"
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
 
 __device__ __forceinline__ int32_t ld32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st32(int32_t* p, int32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-static inline unsigned node_grid(int64_t count) {
-    int64_t g = ceil_div(count > 0 ? count : 1, kBlock);
-    return (unsigned)(g > kMaxGrid ? kMaxGrid : g);
-}
 
 // ------------------------------------------------------------------ weak: union-find
 __global__ __launch_bounds__(kBlock) void k_cc_identity(int32_t* __restrict__ parent, int64_t n) {
@@ -399,7 +395,7 @@ int pp_graph_components(const int64_t* edge_index, int64_t m, int64_t n, const i
         return PP_OK;
     }
     const ComponentsWs w = carve_components(ws, n, strong != 0);
-    const unsigned gn = node_grid(n), gm = node_grid(m);
+    const unsigned gn = capped_grid(n, kBlock), gm = capped_grid(m, kBlock);
     if (m == 0 || !strong) {
         k_cc_identity<<<gn, kBlock, 0, st>>>(w.rep, n);
         PP_LAUNCH_CHECK();
@@ -471,11 +467,11 @@ int pp_graph_component_nodes(const int32_t* labels, int64_t n, int64_t keep, int
         return PP_OK;
     }
     const KeepWs w = carve_keep(ws, n);
-    k_cc_keep_nodes<<<node_grid(n), kBlock, 0, st>>>(labels, n, (int32_t)keep, w.flag);
+    k_cc_keep_nodes<<<capped_grid(n, kBlock), kBlock, 0, st>>>(labels, n, (int32_t)keep, w.flag);
     PP_LAUNCH_CHECK();
     const int rc = exclusive_scan<int32_t, int32_t>(w.flag, n, w.pos, true, count_out, w.scan, w.scan_bytes, st);
     if (rc != PP_OK) return rc;
-    k_cc_put_nodes<<<node_grid(n), kBlock, 0, st>>>(w.flag, w.pos, n, nodes_out, nodes_cap);
+    k_cc_put_nodes<<<capped_grid(n, kBlock), kBlock, 0, st>>>(w.flag, w.pos, n, nodes_out, nodes_cap);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -493,11 +489,11 @@ int pp_graph_component_edges(const int64_t* edge_index, int64_t m, int64_t n, co
         return PP_OK;
     }
     const KeepWs w = carve_keep(ws, m);
-    k_cc_keep_edges<<<node_grid(m), kBlock, 0, st>>>(edge_index, m, n, labels, (int32_t)keep, w.flag);
+    k_cc_keep_edges<<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, n, labels, (int32_t)keep, w.flag);
     PP_LAUNCH_CHECK();
     const int rc = exclusive_scan<int32_t, int32_t>(w.flag, m, w.pos, true, count_out, w.scan, w.scan_bytes, st);
     if (rc != PP_OK) return rc;
-    k_cc_put_edges<<<node_grid(m), kBlock, 0, st>>>(edge_index, m, w.flag, w.pos, new_index, edges_out);
+    k_cc_put_edges<<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, w.flag, w.pos, new_index, edges_out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -28,29 +28,17 @@
 #include "pp_common.h"
 #include "pp_internal.h"
 #include "pp_philox.h"
+#include "pp_rows.h"
 
 namespace pp {
 
 constexpr int kLayoutTile = 256;                       // source positions staged per round: 4 KiB of LDS
-constexpr int64_t kLayoutHeavyMin = 1024;
 constexpr int64_t kLayoutBatch = 16;
 constexpr int64_t kLayoutMaxChunks = 64;
 constexpr int64_t kLayoutFillGrid = 2048;              // workgroups the repulsion grid aims at: 256 CUs x 8 resident workgroups
 constexpr int64_t kLayoutLightParts = kMaxGrid - kBlock, kLayoutHeavyParts = kBlock;
-enum { kLDone = 0, kLIters = 1, kLCur = 2, kLHeavyCount = 3, kLT = 4, kLDt = 5, kLErr = 6, kLStateWords = 8 };   // words 4 .. 6 hold doubles
+enum { kLT = kStateShared, kLDt = 5, kLErr = 6, kLStateWords = 8 };   // after the shared words of pp_rows.h; words 4 .. 6 hold doubles
 
-static inline unsigned layout_grid(int64_t items, int64_t per_block, int64_t cap) {
-    int64_t g = ceil_div(items > 0 ? items : 1, per_block);
-    return (unsigned)(g > cap ? cap : g);
-}
-static int layout_width(int group, int64_t n, int64_t nnz) {
-    if (group > 0) return group;
-    const int64_t mean = n > 0 ? ceil_div(nnz, n) : 1;
-    int w = 4;
-    while (w < kWave && w < mean) w <<= 1;
-    return w;
-}
-static bool layout_width_ok(int group) { return group == 0 || (group >= 1 && group <= kWave && (group & (group - 1)) == 0); }
 static bool layout_block_ok(int block) { return block == 0 || block == 64 || block == 128 || block == 256; }
 static int64_t layout_chunks(int64_t n, int block, int64_t chunks) {
     if (chunks > 0) return chunks;
@@ -67,7 +55,7 @@ struct LayoutArgs {
     const uint8_t* fixed;          // [n] or nullptr
     int64_t n, nnz, heavy_min, chunks, chunk_len;
     double k, threshold;
-    double2 *p0, *p1;              // the positions: state[kLCur] says which is current
+    double2 *p0, *p1;              // the positions: state[kCur] says which is current
     double2* part;                 // [chunks][n] repulsion sums
     double* err_part;              // light workgroups first, heavy ones from `light_parts` on
     int64_t light_parts, heavy_parts;
@@ -77,40 +65,6 @@ struct LayoutArgs {
 
 __device__ __forceinline__ double2* layout_buffer(const LayoutArgs& a, int which) { return which ? a.p1 : a.p0; }
 __device__ __forceinline__ double layout_state_f(const LayoutArgs& a, int word) { return __longlong_as_double(a.state[word]); }
-
-__device__ __forceinline__ void layout_bounds(const LayoutArgs& a, int64_t v, int64_t& lo, int64_t& hi) {
-    int64_t p = a.ptr[v], q = a.ptr[v + 1];
-    p = p < 0 ? 0 : (p > a.nnz ? a.nnz : p);
-    q = q > a.nnz ? a.nnz : q;                                                          // (a pointer is never trusted past the entry array)
-    lo = p;
-    hi = q < p ? p : q;
-}
-
-__device__ __forceinline__ double layout_block_sum(double v, double* scratch) {
-    v = wave_sum(v);
-    __syncthreads();
-    if (lane_id() == 0) scratch[wave_id()] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) t += scratch[w];
-    return t;
-}
-__device__ __forceinline__ double layout_block_max(double v, double* scratch) {
-    v = wave_max(v);
-    __syncthreads();
-    if (lane_id() == 0) scratch[wave_id()] = v;
-    __syncthreads();
-    double t = scratch[0];
-#pragma unroll
-    for (int w = 1; w < kWavesPerBlock; ++w) t = scratch[w] > t ? scratch[w] : t;
-    return t;
-}
-__device__ __forceinline__ double layout_fold_parts(const double* part, int64_t count, double* scratch) {
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += kBlock) s += part[i];
-    return layout_block_sum(s, scratch);
-}
 
 // ------------------------------------------------------------------ the iteration
 __device__ __forceinline__ void layout_pair(double2 pi, double2 pj, double& sx, double& sy) {
@@ -122,8 +76,8 @@ __device__ __forceinline__ void layout_pair(double2 pi, double2 pj, double& sx, 
 
 __global__ __launch_bounds__(kBlock) void k_layout_repulse(LayoutArgs a) {
     __shared__ double2 tile[kLayoutTile];
-    if (a.state[kLDone]) return;                                                        // (uniform in the grid)
-    const double2* p = layout_buffer(a, (int)(a.state[kLCur] & 1));
+    if (a.state[kDone]) return;                                                        // (uniform in the grid)
+    const double2* p = layout_buffer(a, (int)(a.state[kCur] & 1));
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < a.n;
     const double2 pi = live ? p[i] : make_double2(0.0, 0.0);
@@ -189,8 +143,8 @@ __device__ __forceinline__ double layout_finish(const LayoutArgs& a, double2* __
 
 __global__ __launch_bounds__(kBlock) void k_layout_attract_groups(LayoutArgs a, int width) {
     __shared__ double scratch[kWavesPerBlock];
-    if (a.state[kLDone]) return;
-    const int cur = (int)(a.state[kLCur] & 1);
+    if (a.state[kDone]) return;
+    const int cur = (int)(a.state[kCur] & 1);
     const double2* p = layout_buffer(a, cur);
     double2* out = layout_buffer(a, cur ^ 1);
     const double t = layout_state_f(a, kLT);
@@ -204,39 +158,36 @@ __global__ __launch_bounds__(kBlock) void k_layout_attract_groups(LayoutArgs a, 
         double2 pv = make_double2(0.0, 0.0), s = make_double2(0.0, 0.0);
         if (live) {
             int64_t lo, hi;
-            layout_bounds(a, v, lo, hi);
+            row_span(a.ptr, v, a.nnz, lo, hi);
             heavy = hi - lo >= a.heavy_min;
             pv = p[v];
             if (!heavy) s = layout_row_sum(a, p, pv, lo, hi, sub, width);
         }
-        for (int d = width >> 1; d > 0; d >>= 1) {                                      // (partners share the node: both are here)
-            s.x += __shfl_xor(s.x, d, kWave);
-            s.y += __shfl_xor(s.y, d, kWave);
-        }
+        group_sum(width, s.x, s.y);                                                     // (partners share the node: both are here)
         if (live && sub == 0 && !heavy) err += layout_finish(a, out, v, pv, s, t);
     }
-    err = layout_block_sum(err, scratch);
+    err = block_sum_fixed(err, scratch);
     if (threadIdx.x == 0) a.err_part[blockIdx.x] = err;
 }
 
 __global__ __launch_bounds__(kBlock) void k_layout_attract_blocks(LayoutArgs a) {
     __shared__ double scratch[kWavesPerBlock];
-    if (a.state[kLDone]) return;
-    const int cur = (int)(a.state[kLCur] & 1);
+    if (a.state[kDone]) return;
+    const int cur = (int)(a.state[kCur] & 1);
     const double2* p = layout_buffer(a, cur);
     double2* out = layout_buffer(a, cur ^ 1);
     const double t = layout_state_f(a, kLT);
-    const int64_t heavy_count = a.state[kLHeavyCount];
+    const int64_t heavy_count = a.state[kHeavyCount];
     double err = 0.0;                                                                   // (thread 0's is the workgroup's)
     for (int64_t i = blockIdx.x; i < heavy_count; i += gridDim.x) {
         const int64_t v = a.heavy_list[i];
         if ((uint64_t)v >= (uint64_t)a.n) continue;                                     // (uniform in the workgroup)
         int64_t lo, hi;
-        layout_bounds(a, v, lo, hi);
+        row_span(a.ptr, v, a.nnz, lo, hi);
         const double2 pv = p[v];
         double2 s = layout_row_sum(a, p, pv, lo, hi, (int)threadIdx.x, kBlock);
-        s.x = layout_block_sum(s.x, scratch);
-        s.y = layout_block_sum(s.y, scratch);
+        s.x = block_sum_fixed(s.x, scratch);
+        s.y = block_sum_fixed(s.y, scratch);
         if (threadIdx.x == 0) err += layout_finish(a, out, v, pv, s, t);
     }
     if (threadIdx.x == 0) a.err_part[a.light_parts + blockIdx.x] = err;
@@ -244,15 +195,15 @@ __global__ __launch_bounds__(kBlock) void k_layout_attract_blocks(LayoutArgs a) 
 
 __global__ __launch_bounds__(kBlock) void k_layout_decide(LayoutArgs a) {
     __shared__ double scratch[kWavesPerBlock];
-    if (a.state[kLDone]) return;
-    const double total = layout_fold_parts(a.err_part, a.light_parts + a.heavy_parts, scratch);
+    if (a.state[kDone]) return;
+    const double total = fold_parts(a.err_part, a.light_parts + a.heavy_parts, scratch);
     if (threadIdx.x == 0) {
         const double err = sqrt(total) / (double)a.n;
-        a.state[kLIters] += 1;
-        a.state[kLCur] ^= 1;
+        a.state[kIters] += 1;
+        a.state[kCur] ^= 1;
         a.state[kLT] = __double_as_longlong(layout_state_f(a, kLT) - layout_state_f(a, kLDt));
         a.state[kLErr] = __double_as_longlong(err);
-        if (err < a.threshold) a.state[kLDone] = 1;                                     // (false for a NaN)
+        if (err < a.threshold) a.state[kDone] = 1;                                     // (false for a NaN)
     }
 }
 
@@ -267,8 +218,8 @@ __global__ __launch_bounds__(kBlock) void k_layout_extent_parts(const double2* _
         lx = q.x < lx ? q.x : lx; hx = q.x > hx ? q.x : hx;
         ly = q.y < ly ? q.y : ly; hy = q.y > hy ? q.y : hy;
     }
-    lx = -layout_block_max(-lx, scratch); hx = layout_block_max(hx, scratch);
-    ly = -layout_block_max(-ly, scratch); hy = layout_block_max(hy, scratch);
+    lx = -block_max_fixed(-lx, scratch); hx = block_max_fixed(hx, scratch);
+    ly = -block_max_fixed(-ly, scratch); hy = block_max_fixed(hy, scratch);
     if (threadIdx.x == 0) { part[4 * blockIdx.x] = lx; part[4 * blockIdx.x + 1] = hx; part[4 * blockIdx.x + 2] = ly; part[4 * blockIdx.x + 3] = hy; }
 }
 
@@ -280,30 +231,12 @@ __global__ __launch_bounds__(kBlock) void k_layout_temperature(const double* __r
         lx = part[4 * i] < lx ? part[4 * i] : lx; hx = part[4 * i + 1] > hx ? part[4 * i + 1] : hx;
         ly = part[4 * i + 2] < ly ? part[4 * i + 2] : ly; hy = part[4 * i + 3] > hy ? part[4 * i + 3] : hy;
     }
-    lx = -layout_block_max(-lx, scratch); hx = layout_block_max(hx, scratch);
-    ly = -layout_block_max(-ly, scratch); hy = layout_block_max(hy, scratch);
+    lx = -block_max_fixed(-lx, scratch); hx = block_max_fixed(hx, scratch);
+    ly = -block_max_fixed(-ly, scratch); hy = block_max_fixed(hy, scratch);
     if (threadIdx.x == 0) {
         const double ex = hx - lx, ey = hy - ly, t = (ex > ey ? ex : ey) * 0.1;
         state[kLT] = __double_as_longlong(t);
         state[kLDt] = __double_as_longlong(t / (double)(iterations + 1));
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_layout_heavy_flags(const int64_t* __restrict__ ptr, int64_t n, int64_t nnz, int64_t heavy_min,
-                                                              int32_t* __restrict__ flag) {
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        int64_t p = ptr[v], q = ptr[v + 1];
-        p = p < 0 ? 0 : (p > nnz ? nnz : p);
-        q = q > nnz ? nnz : (q < p ? p : q);
-        flag[v] = q - p >= heavy_min;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_layout_heavy_list(const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, int64_t n,
-                                                             int32_t* __restrict__ heavy_list) {
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        const int32_t p = pos[v];
-        if (flag[v] && (uint64_t)p < (uint64_t)n) heavy_list[p] = (int32_t)v;           // (a scan: ascending, one writer per word)
     }
 }
 
@@ -312,7 +245,7 @@ __global__ __launch_bounds__(kBlock) void k_layout_copy(const double2* __restric
 }
 
 __global__ __launch_bounds__(kBlock) void k_layout_result(const LayoutArgs a, double2* __restrict__ pos) {
-    const double2* p = layout_buffer(a, (int)(a.state[kLCur] & 1));
+    const double2* p = layout_buffer(a, (int)(a.state[kCur] & 1));
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < a.n; v += (int64_t)gridDim.x * kBlock) pos[v] = p[v];
 }
 
@@ -348,15 +281,15 @@ __global__ __launch_bounds__(kBlock) void k_layout_sum_parts(const double2* __re
     __shared__ double scratch[kWavesPerBlock];
     double sx = 0.0, sy = 0.0;
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) { sx += p[v].x; sy += p[v].y; }
-    sx = layout_block_sum(sx, scratch);
-    sy = layout_block_sum(sy, scratch);
+    sx = block_sum_fixed(sx, scratch);
+    sy = block_sum_fixed(sy, scratch);
     if (threadIdx.x == 0) { part[blockIdx.x] = sx; part[gridDim.x + blockIdx.x] = sy; }
 }
 
 // p -= mean (every workgroup folds the same partials in the same shape: all hold the same mean); one partial of max |p| per workgroup
 __global__ __launch_bounds__(kBlock) void k_layout_center(double2* __restrict__ p, int64_t n, const double* part, double* __restrict__ lim_part) {
     __shared__ double scratch[kWavesPerBlock];
-    const double mx = layout_fold_parts(part, gridDim.x, scratch) / (double)n, my = layout_fold_parts(part + gridDim.x, gridDim.x, scratch) / (double)n;
+    const double mx = fold_parts(part, gridDim.x, scratch) / (double)n, my = fold_parts(part + gridDim.x, gridDim.x, scratch) / (double)n;
     double lim = 0.0;
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
         const double2 q = make_double2(p[v].x - mx, p[v].y - my);
@@ -364,7 +297,7 @@ __global__ __launch_bounds__(kBlock) void k_layout_center(double2* __restrict__ 
         const double m = fabs(q.x) > fabs(q.y) ? fabs(q.x) : fabs(q.y);
         lim = m > lim ? m : lim;
     }
-    lim = layout_block_max(lim, scratch);
+    lim = block_max_fixed(lim, scratch);
     if (threadIdx.x == 0) lim_part[blockIdx.x] = lim;
 }
 
@@ -372,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_layout_scale(double2* __restrict__ p
     __shared__ double scratch[kWavesPerBlock];
     double lim = 0.0;
     for (int64_t i = threadIdx.x; i < gridDim.x; i += kBlock) lim = lim_part[i] > lim ? lim_part[i] : lim;
-    lim = layout_block_max(lim, scratch);
+    lim = block_max_fixed(lim, scratch);
     const double f = lim > 0.0 ? scale / lim : 1.0;
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock)
         p[v] = make_double2(p[v].x * f + cx, p[v].y * f + cy);
@@ -487,7 +420,7 @@ static LayoutAdjWs carve_layout_adj(void* ws, int64_t m) {
 
 extern "C" {
 
-int64_t pp_graph_layout_heavy_min(void) { return pp::kLayoutHeavyMin; }
+int64_t pp_graph_layout_heavy_min(void) { return pp::kHeavyMinDefault; }
 
 int64_t pp_graph_layout_chunks(int64_t n, int block, int64_t chunks) { return pp::layout_chunks(n, block, chunks); }
 
@@ -506,7 +439,7 @@ int pp_graph_layout_iterate(const int64_t* ptr, const int64_t* nbr, const double
     PP_REQUIRE(iterations >= 0 && batch >= 0, PP_ERR_ARG, "pp_graph_layout_iterate: iterations and batch must be >= 0");
     PP_REQUIRE(layout_block_ok(block), PP_ERR_ARG, "pp_graph_layout_iterate: block must be 0, 64, 128 or 256");
     PP_REQUIRE(chunks >= 0 && chunks <= kLayoutMaxChunks, PP_ERR_ARG, "pp_graph_layout_iterate: chunks must be 0 .. %lld", (long long)kLayoutMaxChunks);
-    PP_REQUIRE(layout_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_layout_iterate: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_layout_iterate: group must be 0 or a power of two up to 64");
     PP_REQUIRE(n == 0 || (pos && ptr), PP_ERR_ARG, "pp_graph_layout_iterate: pos and ptr are required");
     PP_REQUIRE(nnz == 0 || nbr, PP_ERR_ARG, "pp_graph_layout_iterate: nbr is required");
     PP_REQUIRE(ws_bytes >= pp_graph_layout_ws_bytes(n, block, chunks), PP_ERR_WORKSPACE, "pp_graph_layout_iterate: workspace too small");
@@ -518,13 +451,13 @@ int pp_graph_layout_iterate(const int64_t* ptr, const int64_t* nbr, const double
     const int threads = block > 0 ? block : kBlock;
     const int64_t n_chunks = layout_chunks(n, block, chunks);
     const LayoutWs s = carve_layout(ws, n, n_chunks);
-    const int width = layout_width(group, n, nnz);
-    const unsigned gn = layout_grid(n, kBlock, kLayoutLightParts);
+    const int width = row_width(group, n, nnz);
+    const unsigned gn = capped_grid(n, kBlock, kLayoutLightParts);
     int64_t host[kLStateWords] = {0};
 
     LayoutArgs a{};
     a.ptr = ptr; a.nbr = nbr; a.w = w; a.fixed = fixed; a.n = n; a.nnz = nnz;
-    a.heavy_min = heavy_min > 0 ? heavy_min : kLayoutHeavyMin;
+    a.heavy_min = heavy_min > 0 ? heavy_min : kHeavyMinDefault;
     a.chunks = n_chunks;
     a.chunk_len = ceil_div(n, n_chunks);
     a.k = k; a.threshold = threshold;
@@ -534,12 +467,8 @@ int pp_graph_layout_iterate(const int64_t* ptr, const int64_t* nbr, const double
     __builtin_memcpy(&host[kLT], &t, sizeof(double));
     __builtin_memcpy(&host[kLDt], &dt, sizeof(double));
     PP_HIP(hipMemcpyAsync(s.state, host, kLStateWords * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    k_layout_heavy_flags<<<gn, kBlock, 0, st>>>(ptr, n, nnz, a.heavy_min, s.flag);
-    PP_LAUNCH_CHECK();
-    int rc = exclusive_scan<int32_t, int32_t>(s.flag, n, s.pos, true, s.state + kLHeavyCount, s.scan, s.scan_bytes, st);
+    int rc = heavy_rows_ascending(ptr, n, nnz, a.heavy_min, s.flag, s.pos, s.heavy_list, s.state + kHeavyCount, s.scan, s.scan_bytes, st);
     if (rc != PP_OK) return rc;
-    k_layout_heavy_list<<<gn, kBlock, 0, st>>>(s.flag, s.pos, n, s.heavy_list);
-    PP_LAUNCH_CHECK();
     k_layout_copy<<<gn, kBlock, 0, st>>>((const double2*)pos, n, s.p0);
     PP_LAUNCH_CHECK();
     if (auto_t) {
@@ -550,37 +479,30 @@ int pp_graph_layout_iterate(const int64_t* ptr, const int64_t* nbr, const double
     }
     PP_HIP(hipMemcpyAsync(host, s.state, kLStateWords * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     PP_HIP(hipStreamSynchronize(st));
-    const int64_t heavy_count = host[kLHeavyCount] < 0 ? 0 : (host[kLHeavyCount] > n ? n : host[kLHeavyCount]);
+    const int64_t heavy_count = host[kHeavyCount] < 0 ? 0 : (host[kHeavyCount] > n ? n : host[kHeavyCount]);
 
     const dim3 g_repulse((unsigned)ceil_div(n, threads), (unsigned)n_chunks);
-    const unsigned g_light = layout_grid(n, kBlock / width, kLayoutLightParts);
-    const unsigned g_heavy = heavy_count > 0 ? layout_grid(heavy_count, 1, kLayoutHeavyParts) : 0;
+    const unsigned g_light = capped_grid(n, kBlock / width, kLayoutLightParts);
+    const unsigned g_heavy = heavy_count > 0 ? capped_grid(heavy_count, 1, kLayoutHeavyParts) : 0;
     a.light_parts = g_light;
     a.heavy_parts = g_heavy;
     grids[0] = g_repulse.x; grids[1] = g_repulse.y; grids[2] = g_light; grids[3] = g_heavy;
 
-    const int64_t per_batch = batch > 0 ? batch : kLayoutBatch;
-    int64_t enqueued = 0;
-    while (enqueued < iterations) {
-        const int64_t now = iterations - enqueued < per_batch ? iterations - enqueued : per_batch;
-        for (int64_t i = 0; i < now; ++i) {
-            k_layout_repulse<<<g_repulse, threads, 0, st>>>(a);
-            PP_LAUNCH_CHECK();
-            k_layout_attract_groups<<<g_light, kBlock, 0, st>>>(a, width);
-            PP_LAUNCH_CHECK();
-            if (g_heavy > 0) {
-                k_layout_attract_blocks<<<g_heavy, kBlock, 0, st>>>(a);
-                PP_LAUNCH_CHECK();
-            }
-            k_layout_decide<<<1, kBlock, 0, st>>>(a);
+    rc = run_batched(iterations, batch > 0 ? batch : kLayoutBatch, s.state, host, kLStateWords, st, [&]() -> int {
+        k_layout_repulse<<<g_repulse, threads, 0, st>>>(a);
+        PP_LAUNCH_CHECK();
+        k_layout_attract_groups<<<g_light, kBlock, 0, st>>>(a, width);
+        PP_LAUNCH_CHECK();
+        if (g_heavy > 0) {
+            k_layout_attract_blocks<<<g_heavy, kBlock, 0, st>>>(a);
             PP_LAUNCH_CHECK();
         }
-        enqueued += now;
-        PP_HIP(hipMemcpyAsync(host, s.state, kLStateWords * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
-        if (host[kLDone]) break;
-    }
-    *iterations_run = host[kLIters];
+        k_layout_decide<<<1, kBlock, 0, st>>>(a);
+        PP_LAUNCH_CHECK();
+        return PP_OK;
+    });
+    if (rc != PP_OK) return rc;
+    *iterations_run = host[kIters];
     __builtin_memcpy(last_err, &host[kLErr], sizeof(double));
     k_layout_result<<<gn, kBlock, 0, st>>>(a, (double2*)pos);
     PP_LAUNCH_CHECK();
@@ -596,7 +518,7 @@ int pp_graph_layout_rescale(double* pos, int64_t n, double scale, double cx, dou
     if (n == 0) return PP_OK;
     PP_REQUIRE(pos && ws, PP_ERR_ARG, "pp_graph_layout_rescale: null pointer");
     hipStream_t st = (hipStream_t)stream;
-    const unsigned g = layout_grid(n, kBlock, kMaxGrid);
+    const unsigned g = capped_grid(n, kBlock);
     double* part = (double*)ws;
     k_layout_sum_parts<<<g, kBlock, 0, st>>>((const double2*)pos, n, part);
     PP_LAUNCH_CHECK();
@@ -613,8 +535,8 @@ int pp_graph_layout_start(int64_t seed, int64_t n, double dom_size, double cx, d
     PP_REQUIRE(n >= 0 && n < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_graph_layout_start: n outside [0, 2^31 - 1)");
     if (n == 0) return PP_OK;
     PP_REQUIRE(pos && (given || !has), PP_ERR_ARG, "pp_graph_layout_start: null pointer");
-    k_layout_start<<<layout_grid(n, kBlock, kMaxGrid), kBlock, 0, (hipStream_t)stream>>>((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), n, dom_size, cx,
-                                                                                        cy, (const double2*)given, has, (double2*)pos);
+    k_layout_start<<<capped_grid(n, kBlock), kBlock, 0, (hipStream_t)stream>>>((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), n, dom_size, cx,
+                                                                               cy, (const double2*)given, has, (double2*)pos);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -624,8 +546,8 @@ int pp_graph_layout_random(int64_t seed, int64_t n, float cx, float cy, float* p
     PP_REQUIRE(n >= 0 && n < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_graph_layout_random: n outside [0, 2^31 - 1)");
     if (n == 0) return PP_OK;
     PP_REQUIRE(pos, PP_ERR_ARG, "pp_graph_layout_random: null pointer");
-    k_layout_random_f32<<<layout_grid(n, kBlock, kMaxGrid), kBlock, 0, (hipStream_t)stream>>>((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), n, cx, cy,
-                                                                                             (float2*)pos);
+    k_layout_random_f32<<<capped_grid(n, kBlock), kBlock, 0, (hipStream_t)stream>>>((uint32_t)seed, (uint32_t)((uint64_t)seed >> 32), n, cx, cy,
+                                                                                    (float2*)pos);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -636,7 +558,7 @@ int pp_graph_layout_closed_form(int kind, int64_t n, double* pos, pp_stream_t st
     PP_REQUIRE(n >= 0 && n < (int64_t)0x7fffffff, PP_ERR_TOO_LARGE, "pp_graph_layout_closed_form: n outside [0, 2^31 - 1)");
     if (n == 0) return PP_OK;
     PP_REQUIRE(pos, PP_ERR_ARG, "pp_graph_layout_closed_form: null pointer");
-    k_layout_closed_form<<<layout_grid(n, kBlock, kMaxGrid), kBlock, 0, (hipStream_t)stream>>>(kind, n, (double2*)pos);
+    k_layout_closed_form<<<capped_grid(n, kBlock), kBlock, 0, (hipStream_t)stream>>>(kind, n, (double2*)pos);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -655,11 +577,11 @@ int pp_graph_layout_adj_count(const int64_t* edge_index, int64_t m, int64_t n, i
     hipStream_t st = (hipStream_t)stream;
     const LayoutAdjWs w = carve_layout_adj(ws, m);
     const int64_t count = 2 * m;
-    k_layout_adj_keys<<<layout_grid(m, kBlock, kMaxGrid), kBlock, 0, st>>>(edge_index, m, n, w.key);
+    k_layout_adj_keys<<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, n, w.key);
     PP_LAUNCH_CHECK();
     int rc = sort_pairs<uint64_t>(w.key, nullptr, w.sorted, w.entry, count, 0, bits_for((uint64_t)n * (uint64_t)n), w.sort, w.sort_bytes, st);
     if (rc != PP_OK) return rc;
-    k_layout_adj_flags<<<layout_grid(count, kBlock, kMaxGrid), kBlock, 0, st>>>(w.sorted, count, n, w.flag);
+    k_layout_adj_flags<<<capped_grid(count, kBlock), kBlock, 0, st>>>(w.sorted, count, n, w.flag);
     PP_LAUNCH_CHECK();
     rc = exclusive_scan<int32_t, int64_t>(w.flag, count, w.pos, true, w.total, w.scan, w.scan_bytes, st);
     if (rc != PP_OK) return rc;
@@ -682,9 +604,9 @@ int pp_graph_layout_adj_fill(const double* weight, int64_t m, int64_t n, int64_t
     }
     PP_REQUIRE(nbr && w && ws, PP_ERR_ARG, "pp_graph_layout_adj_fill: null pointer");
     const LayoutAdjWs s = carve_layout_adj(ws, m);
-    k_layout_adj_fill<<<layout_grid(2 * m, kBlock, kMaxGrid), kBlock, 0, st>>>(s.sorted, s.entry, s.flag, s.pos, 2 * m, n, m, nnz, weight, s.row, nbr, w);
+    k_layout_adj_fill<<<capped_grid(2 * m, kBlock), kBlock, 0, st>>>(s.sorted, s.entry, s.flag, s.pos, 2 * m, n, m, nnz, weight, s.row, nbr, w);
     PP_LAUNCH_CHECK();
-    k_layout_adj_ptr<<<layout_grid(nnz, kBlock, kMaxGrid), kBlock, 0, st>>>(s.row, nnz, n, ptr);
+    k_layout_adj_ptr<<<capped_grid(nnz, kBlock), kBlock, 0, st>>>(s.row, nnz, n, ptr);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -7,7 +7,7 @@
 //   Katz       : x'[v] = alpha * (sum_u w(u, v) x[u]) + b[v];                   err = sum |x' - x|;  result x' * (1 / sqrt(sum x'^2))
 // Launches of one iteration — 2 (Katz, no heavy row) to 4 (eigenvector with heavy rows), all plain, on one stream; no cooperative launch,
 // no grid barrier, no floating-point atomic:
-//   1. k_power_gather_groups: a row belongs to a GROUP of `width` lanes (work split of pp_graph_wl.hip); lane j adds entries j, j + width, ...
+//   1. k_power_gather_groups: a row belongs to a GROUP of `width` lanes (work split of pp_rows.h); lane j adds entries j, j + width, ...
 //      in order, the lanes fold by a butterfly.  A row of heavy_min entries or more is left to
 //   2. k_power_gather_blocks (only if there are heavy rows): a whole workgroup per row, thread j adds entries j, j + 256, ...
 //      Both write the new vector and one partial per workgroup: sum y^2, and for Katz sum |x' - x|.
@@ -24,27 +24,14 @@
 // in order).  The grids depend on n, width and the number of heavy rows; the list of heavy rows is built by a scan, ascending.
 #include "pp_common.h"
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
 
-constexpr int64_t kPowerHeavyMin = 1024;
 constexpr int64_t kPowerBatch = 16, kPowerBatchMin = 8;
 constexpr int64_t kPowerLightParts = kMaxGrid - kBlock;   // workgroups of the light gather (and of k_power_scale)
 constexpr int64_t kPowerHeavyParts = kBlock;              // workgroups of the heavy gather
-enum { kDone = 0, kIters = 1, kCur = 2, kHeavyCount = 3, kStateWords = 8 };
-
-static inline unsigned power_grid(int64_t items, int64_t per_block, int64_t cap) {
-    int64_t g = ceil_div(items > 0 ? items : 1, per_block);
-    return (unsigned)(g > cap ? cap : g);
-}
-static int power_width(int group, int64_t n, int64_t k) {
-    if (group > 0) return group;
-    const int64_t mean = n > 0 ? ceil_div(k, n) : 1;
-    int w = 4;
-    while (w < kWave && w < mean) w <<= 1;
-    return w;
-}
-static bool power_width_ok(int group) { return group == 0 || (group >= 1 && group <= kWave && (group & (group - 1)) == 0); }
+constexpr int kStateWords = 8;                            // the shared words of pp_rows.h; none of its own
 
 struct PowerArgs {
     const int64_t* col_ptr;        // [n + 1] predecessor lists
@@ -66,14 +53,6 @@ struct PowerArgs {
 
 __device__ __forceinline__ double* power_buffer(const PowerArgs& a, int which) { return which ? a.x1 : a.x0; }
 
-__device__ __forceinline__ void power_bounds(const PowerArgs& a, int64_t v, int64_t& lo, int64_t& hi) {
-    int64_t p = a.col_ptr[v], q = a.col_ptr[v + 1];
-    p = p < 0 ? 0 : (p > a.k ? a.k : p);
-    q = q > a.k ? a.k : q;                                                              // (a pointer is never trusted past the entry array)
-    lo = p;
-    hi = q < p ? p : q;
-}
-
 // entries lo + sub, lo + sub + step, ... of one predecessor list, added in that order
 __device__ __forceinline__ double power_row_sum(const PowerArgs& a, const double* __restrict__ x, int64_t lo, int64_t hi, int sub, int step) {
     double s = 0.0;
@@ -84,25 +63,6 @@ __device__ __forceinline__ double power_row_sum(const PowerArgs& a, const double
         s += a.weight ? load_stream(a.weight + i) * xu : xu;
     }
     return s;
-}
-
-// all threads of the workgroup get s(thread 0..255) folded in a fixed shape: wave butterfly, then the waves in order
-__device__ __forceinline__ double power_block_sum(double v, double* scratch) {
-    v = wave_sum(v);
-    __syncthreads();                                                                    // (scratch may still be read from the previous fold)
-    if (lane_id() == 0) scratch[wave_id()] = v;
-    __syncthreads();
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < kWavesPerBlock; ++w) t += scratch[w];
-    return t;
-}
-
-// partials part[0 .. count) folded by workgroup index in a fixed shape; the same bits in every thread of every workgroup that asks
-__device__ __forceinline__ double power_fold_parts(const double* part, int64_t count, double* scratch) {
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += kBlock) s += part[i];
-    return power_block_sum(s, scratch);
 }
 
 // the new value of node v from its row sum
@@ -127,11 +87,11 @@ __global__ __launch_bounds__(kBlock) void k_power_gather_groups(PowerArgs a, int
         bool heavy = false;
         double s = 0.0;
         if (live) {
-            power_bounds(a, v, lo, hi);
+            row_span(a.col_ptr, v, a.k, lo, hi);
             heavy = hi - lo >= a.heavy_min;
             if (!heavy) s = power_row_sum(a, x, lo, hi, sub, width);
         }
-        for (int d = width >> 1; d > 0; d >>= 1) s += __shfl_xor(s, d, kWave);          // (partners share the node: both are here)
+        group_sum(width, s);                                                            // (partners share the node: both are here)
         if (live && sub == 0 && !heavy) {
             const double xv = x[v], y = power_value(a, xv, v, s);
             out[v] = y;
@@ -139,8 +99,8 @@ __global__ __launch_bounds__(kBlock) void k_power_gather_groups(PowerArgs a, int
             if (a.mode == PP_POWER_KATZ) err += fabs(y - xv);
         }
     }
-    sq = power_block_sum(sq, scratch);
-    err = power_block_sum(err, scratch);
+    sq = block_sum_fixed(sq, scratch);
+    err = block_sum_fixed(err, scratch);
     if (threadIdx.x == 0) { a.sq_part[blockIdx.x] = sq; a.err_part[blockIdx.x] = err; }
 }
 
@@ -156,8 +116,8 @@ __global__ __launch_bounds__(kBlock) void k_power_gather_blocks(PowerArgs a) {
         const int64_t v = a.heavy_list[i];
         if ((uint64_t)v >= (uint64_t)a.n) continue;                                     // (uniform in the workgroup)
         int64_t lo, hi;
-        power_bounds(a, v, lo, hi);
-        const double s = power_block_sum(power_row_sum(a, x, lo, hi, (int)threadIdx.x, kBlock), scratch);
+        row_span(a.col_ptr, v, a.k, lo, hi);
+        const double s = block_sum_fixed(power_row_sum(a, x, lo, hi, (int)threadIdx.x, kBlock), scratch);
         if (threadIdx.x == 0) {
             const double xv = x[v], y = power_value(a, xv, v, s);
             out[v] = y;
@@ -175,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void k_power_scale(PowerArgs a) {
     const int cur = (int)(a.state[kCur] & 1);
     const double* x = power_buffer(a, cur);
     double* out = power_buffer(a, cur ^ 1);
-    double norm = sqrt(power_fold_parts(a.sq_part, a.light_parts + a.heavy_parts, scratch));
+    double norm = sqrt(fold_parts(a.sq_part, a.light_parts + a.heavy_parts, scratch));
     if (norm == 0.0) norm = 1.0;                                                        // (networkx: `hypot(...) or 1`; a NaN stays)
     double err = 0.0;
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < a.n; v += (int64_t)gridDim.x * kBlock) {
@@ -183,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void k_power_scale(PowerArgs a) {
         out[v] = xn;
         err += fabs(xn - x[v]);
     }
-    err = power_block_sum(err, scratch);
+    err = block_sum_fixed(err, scratch);
     if (threadIdx.x == 0) a.err_part[blockIdx.x] = err;
 }
 
@@ -191,10 +151,10 @@ __global__ __launch_bounds__(kBlock) void k_power_decide(PowerArgs a) {
     __shared__ double scratch[kWavesPerBlock];
     if (a.state[kDone]) return;
     const int64_t parts = a.mode == PP_POWER_EIGENVECTOR ? a.scale_parts : a.light_parts + a.heavy_parts;
-    const double err = power_fold_parts(a.err_part, parts, scratch);
+    const double err = fold_parts(a.err_part, parts, scratch);
     double factor = 1.0;
     if (a.mode == PP_POWER_KATZ && a.normalized) {
-        const double norm = sqrt(power_fold_parts(a.sq_part, parts, scratch));
+        const double norm = sqrt(fold_parts(a.sq_part, parts, scratch));
         if (norm != 0.0) factor = 1.0 / norm;                                           // (networkx: a ZeroDivisionError leaves the factor 1)
     }
     if (threadIdx.x == 0) {
@@ -217,33 +177,15 @@ __global__ __launch_bounds__(kBlock) void k_power_start(const double* __restrict
         x[v] = t;
         s += t;
     }
-    s = power_block_sum(s, scratch);
+    s = block_sum_fixed(s, scratch);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
 // eigenvector: x = start / sum(start)
 __global__ __launch_bounds__(kBlock) void k_power_start_scale(double* __restrict__ x, int64_t n, const double* part, int64_t parts) {
     __shared__ double scratch[kWavesPerBlock];
-    const double total = power_fold_parts(part, parts, scratch);
+    const double total = fold_parts(part, parts, scratch);
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) x[v] = x[v] / total;
-}
-
-__global__ __launch_bounds__(kBlock) void k_power_heavy_flags(const int64_t* __restrict__ col_ptr, int64_t n, int64_t k, int64_t heavy_min,
-                                                             int32_t* __restrict__ flag) {
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        int64_t p = col_ptr[v], q = col_ptr[v + 1];
-        p = p < 0 ? 0 : (p > k ? k : p);
-        q = q > k ? k : (q < p ? p : q);
-        flag[v] = q - p >= heavy_min;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void k_power_heavy_list(const int32_t* __restrict__ flag, const int32_t* __restrict__ pos, int64_t n,
-                                                            int32_t* __restrict__ heavy_list) {
-    for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        const int32_t p = pos[v];
-        if (flag[v] && (uint64_t)p < (uint64_t)n) heavy_list[p] = (int32_t)v;           // (a scan: ascending, one writer per word)
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void k_power_result(const PowerArgs a, double* __restrict__ values) {
@@ -283,7 +225,7 @@ static PowerWs carve_power(void* ws, int64_t n) {
 
 extern "C" {
 
-int64_t pp_graph_power_heavy_min(void) { return pp::kPowerHeavyMin; }
+int64_t pp_graph_power_heavy_min(void) { return pp::kHeavyMinDefault; }
 
 size_t pp_graph_power_ws_bytes(int64_t n) { return pp::carve_power(nullptr, n > 0 ? n : 0).total; }
 
@@ -298,7 +240,7 @@ int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const dou
     PP_REQUIRE(iterations && converged && grids, PP_ERR_ARG, "pp_graph_power_iterate: iterations, converged and grids are required");
     PP_REQUIRE(max_iter >= 1, PP_ERR_ARG, "pp_graph_power_iterate: max_iter must be >= 1");
     PP_REQUIRE(batch == 0 || batch >= kPowerBatchMin, PP_ERR_ARG, "pp_graph_power_iterate: batch must be 0 or >= %lld", (long long)kPowerBatchMin);
-    PP_REQUIRE(power_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_power_iterate: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_power_iterate: group must be 0 or a power of two up to 64");
     PP_REQUIRE(n == 0 || (values && col_ptr), PP_ERR_ARG, "pp_graph_power_iterate: values and col_ptr are required");
     PP_REQUIRE(k == 0 || row, PP_ERR_ARG, "pp_graph_power_iterate: row is required");
     PP_REQUIRE(ws_bytes >= pp_graph_power_ws_bytes(n), PP_ERR_WORKSPACE, "pp_graph_power_iterate: workspace too small");
@@ -308,13 +250,13 @@ int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const dou
     if (n == 0) return PP_OK;
     hipStream_t st = (hipStream_t)stream;
     const PowerWs w = carve_power(ws, n);
-    const int width = power_width(group, n, k);
-    const unsigned gn = power_grid(n, kBlock, kPowerLightParts);
+    const int width = row_width(group, n, k);
+    const unsigned gn = capped_grid(n, kBlock, kPowerLightParts);
     int64_t host[kStateWords] = {0};
 
     PowerArgs a{};
     a.col_ptr = col_ptr; a.row = row; a.weight = weight; a.beta = beta; a.n = n; a.k = k;
-    a.heavy_min = heavy_min > 0 ? heavy_min : kPowerHeavyMin;
+    a.heavy_min = heavy_min > 0 ? heavy_min : kHeavyMinDefault;
     a.mode = mode; a.normalized = normalized; a.alpha = alpha; a.beta_scalar = beta_scalar; a.threshold = threshold;
     a.x0 = w.x0; a.x1 = w.x1; a.y = w.y; a.sq_part = w.sq_part; a.err_part = w.err_part;
     a.heavy_list = w.heavy_list; a.state = w.state; a.scale = w.scale;
@@ -322,12 +264,8 @@ int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const dou
 
     // set-up: the heavy rows (ascending, by a scan), the start vector; one read-back
     PP_HIP(hipMemsetAsync(w.state, 0, kStateWords * sizeof(int64_t), st));
-    k_power_heavy_flags<<<gn, kBlock, 0, st>>>(col_ptr, n, k, a.heavy_min, w.flag);
-    PP_LAUNCH_CHECK();
-    int rc = exclusive_scan<int32_t, int32_t>(w.flag, n, w.pos, true, w.state + kHeavyCount, w.scan, w.scan_bytes, st);
+    int rc = heavy_rows_ascending(col_ptr, n, k, a.heavy_min, w.flag, w.pos, w.heavy_list, w.state + kHeavyCount, w.scan, w.scan_bytes, st);
     if (rc != PP_OK) return rc;
-    k_power_heavy_list<<<gn, kBlock, 0, st>>>(w.flag, w.pos, n, w.heavy_list);
-    PP_LAUNCH_CHECK();
     k_power_start<<<gn, kBlock, 0, st>>>(start, mode == PP_POWER_EIGENVECTOR ? 1.0 : 0.0, n, w.x0, w.err_part);
     PP_LAUNCH_CHECK();
     if (mode == PP_POWER_EIGENVECTOR) {
@@ -340,36 +278,29 @@ int pp_graph_power_iterate(const int64_t* col_ptr, const int64_t* row, const dou
     PP_HIP(hipStreamSynchronize(st));
     const int64_t heavy_count = host[kHeavyCount] < 0 ? 0 : (host[kHeavyCount] > n ? n : host[kHeavyCount]);
 
-    const unsigned g_light = power_grid(n, kBlock / width, kPowerLightParts);
-    const unsigned g_heavy = heavy_count > 0 ? power_grid(heavy_count, 1, kPowerHeavyParts) : 0;
+    const unsigned g_light = capped_grid(n, kBlock / width, kPowerLightParts);
+    const unsigned g_heavy = heavy_count > 0 ? capped_grid(heavy_count, 1, kPowerHeavyParts) : 0;
     a.light_parts = g_light;
     a.heavy_parts = g_heavy;
     grids[0] = g_light;
     grids[1] = g_heavy;
 
-    const int64_t per_batch = batch > 0 ? batch : kPowerBatch;
-    int64_t enqueued = 0;
-    while (enqueued < max_iter) {
-        const int64_t now = max_iter - enqueued < per_batch ? max_iter - enqueued : per_batch;
-        for (int64_t i = 0; i < now; ++i) {
-            k_power_gather_groups<<<g_light, kBlock, 0, st>>>(a, width);
-            PP_LAUNCH_CHECK();
-            if (g_heavy > 0) {
-                k_power_gather_blocks<<<g_heavy, kBlock, 0, st>>>(a);
-                PP_LAUNCH_CHECK();
-            }
-            if (mode == PP_POWER_EIGENVECTOR) {
-                k_power_scale<<<gn, kBlock, 0, st>>>(a);
-                PP_LAUNCH_CHECK();
-            }
-            k_power_decide<<<1, kBlock, 0, st>>>(a);
+    rc = run_batched(max_iter, batch > 0 ? batch : kPowerBatch, w.state, host, kStateWords, st, [&]() -> int {
+        k_power_gather_groups<<<g_light, kBlock, 0, st>>>(a, width);
+        PP_LAUNCH_CHECK();
+        if (g_heavy > 0) {
+            k_power_gather_blocks<<<g_heavy, kBlock, 0, st>>>(a);
             PP_LAUNCH_CHECK();
         }
-        enqueued += now;
-        PP_HIP(hipMemcpyAsync(host, w.state, kStateWords * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        PP_HIP(hipStreamSynchronize(st));
-        if (host[kDone]) break;
-    }
+        if (mode == PP_POWER_EIGENVECTOR) {
+            k_power_scale<<<gn, kBlock, 0, st>>>(a);
+            PP_LAUNCH_CHECK();
+        }
+        k_power_decide<<<1, kBlock, 0, st>>>(a);
+        PP_LAUNCH_CHECK();
+        return PP_OK;
+    });
+    if (rc != PP_OK) return rc;
     *iterations = host[kIters];
     *converged = host[kDone] ? 1 : 0;
     k_power_result<<<gn, kBlock, 0, st>>>(a, values);

@@ -8,9 +8,9 @@
 // Over the entries e = (v, x) of the structure it is the number of closed triads (x, y) of v that start with x — the reference's set, self-loops
 // included: x = v and y = x are members of the lists like any other — and the per-node count is a difference of the scan of these numbers.
 //
-// Work split: a task (one pair of lists) belongs to a GROUP of `width` lanes (a power of two, 1 .. 64, one value per launch, chosen by the host
-// from the mean length of a list).  Lane r of the group takes the entries r, r + width, ... of the SHORTER list and bisects the longer one; a
-// lane's keys ascend, so every search starts where the last one ended.  Cost: min(d) / width searches of log(max d) steps per lane.  A task
+// Work split (pp_rows.h): a task (one pair of lists) belongs to a GROUP of `width` lanes (a power of two, 1 .. 64, one value per launch,
+// chosen by the host from the mean length of a list).  Lane r of the group takes the entries r, r + width, ... of the SHORTER list and
+// bisects the longer one; a lane's keys ascend, so every search starts where the last one ended.  Cost: min(d) / width searches of log(max d) steps per lane.  A task
 // whose shorter list has `heavy_min` entries or more is not walked by its group: the group's first lane appends it to a list (one integer
 // atomic), and a second launch gives every listed task a whole workgroup.  The list's order depends on scheduling; no output does: every task
 // writes its own words, the integers are exact and the float64 sum `aa` has a fixed shape for given width and heavy_min — a lane adds its terms
@@ -18,13 +18,9 @@
 // Node indices outside [0, n) are never dereferenced (such a task meets an empty list) and a row pointer is clamped to the entry array.
 #include "pp_common.h"
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
-
-static inline unsigned triad_grid(int64_t items, int64_t per_block) {
-    int64_t g = ceil_div(items > 0 ? items : 1, per_block);
-    return (unsigned)(g > kMaxGrid ? kMaxGrid : g);
-}
 
 struct MeetArgs {
     const int64_t *row_ptr, *col, *mult;   // the simple structure; mult == nullptr: every multiplicity is 1
@@ -48,12 +44,7 @@ struct Meet {
 
 __device__ __forceinline__ void row_bounds(const MeetArgs& a, int64_t v, int64_t& lo, int64_t& hi) {
     lo = hi = 0;
-    if ((uint64_t)v >= (uint64_t)a.n) return;
-    int64_t p = a.row_ptr[v], q = a.row_ptr[v + 1];
-    p = p < 0 ? 0 : (p > a.ms ? a.ms : p);
-    q = q > a.ms ? a.ms : q;
-    lo = p;
-    hi = q < p ? p : q;
+    if ((uint64_t)v < (uint64_t)a.n) row_span(a.row_ptr, v, a.ms, lo, hi);               // (a node outside [0, n): an empty list)
 }
 
 // The walk shared by every kernel below: lane `rank` of `width` takes every width-th entry of [a0, a1) and bisects [b0, b1).
@@ -112,11 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_meet_groups(MeetArgs a, int width, i
             heavy = a1 - a0 >= heavy_min;
             if (!heavy) meet_lists(a, a0, a1, b0, b1, rank, width, acc);
         }
-        for (int d = width >> 1; d > 0; d >>= 1) {                                     // (partners share the task: both are here)
-            acc.common += __shfl_xor(acc.common, d, kWave);
-            acc.dot += __shfl_xor(acc.dot, d, kWave);
-            acc.aa += __shfl_xor(acc.aa, d, kWave);
-        }
+        group_sum(width, acc.common, acc.dot, acc.aa);                                  // (partners share the task: both are here)
         if (live && rank == 0) {
             if (heavy) a.heavy_list[atomicAdd(a.heavy_count, 1ull)] = task;             // (each task at most once: the list holds `tasks` entries)
             else put_meet(a, task, acc);
@@ -161,24 +148,13 @@ __global__ __launch_bounds__(kBlock) void k_meet_blocks(MeetArgs a) {
 static int run_meet(const MeetArgs& a, int width, int64_t heavy_min, hipStream_t st) {
     PP_HIP(hipMemsetAsync(a.heavy_count, 0, sizeof(unsigned long long), st));
     if (a.tasks == 0) return PP_OK;
-    k_meet_groups<<<triad_grid(a.tasks, kBlock / width), kBlock, 0, st>>>(a, width, heavy_min);
+    k_meet_groups<<<capped_grid(a.tasks, kBlock / width), kBlock, 0, st>>>(a, width, heavy_min);
     PP_LAUNCH_CHECK();
-    const unsigned blocks = triad_grid(a.tasks, 1);
+    const unsigned blocks = capped_grid(a.tasks, 1);
     k_meet_blocks<<<blocks > 512u ? 512u : blocks, kBlock, 0, st>>>(a);                  // (reads the list's length on the device: no read-back)
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
-
-// width: the smallest power of two that is no less than the mean length of a list, between 4 and a wave
-static int pick_width(int group, int64_t n, int64_t ms) {
-    if (group > 0) return group;
-    const int64_t mean = n > 0 ? ceil_div(ms, n) : 1;
-    int w = 4;
-    while (w < kWave && w < mean) w <<= 1;
-    return w;
-}
-static bool width_ok(int group) { return group == 0 || (group >= 1 && group <= kWave && (group & (group - 1)) == 0); }
-constexpr int64_t kHeavyMin = 1024;
 
 // ------------------------------------------------------------------ is the stored edge list the simple structure already?
 __global__ __launch_bounds__(kBlock) void k_count_unordered(const int64_t* __restrict__ edge_index, int64_t m, unsigned long long* out) {
@@ -195,10 +171,9 @@ __global__ __launch_bounds__(kBlock) void k_count_unordered(const int64_t* __res
 __global__ __launch_bounds__(kBlock) void k_row_totals(const int64_t* __restrict__ row_ptr, const int64_t* __restrict__ scan, int64_t n,
                                                       int64_t ms, int64_t* __restrict__ out) {
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        int64_t p = row_ptr[v], q = row_ptr[v + 1];
-        p = p < 0 ? 0 : (p > ms ? ms : p);
-        q = q > ms ? ms : (q < p ? p : q);
-        out[v] = scan[q] - scan[p];
+        int64_t lo, hi;
+        row_span(row_ptr, v, ms, lo, hi);
+        out[v] = scan[hi] - scan[lo];
     }
 }
 
@@ -336,7 +311,7 @@ int pp_graph_count_unordered(const int64_t* edge_index, int64_t m, int64_t* out,
     hipStream_t st = (hipStream_t)stream;
     PP_HIP(hipMemsetAsync(out, 0, sizeof(int64_t), st));
     if (m < 2) return PP_OK;
-    k_count_unordered<<<triad_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, (unsigned long long*)out);
+    k_count_unordered<<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, (unsigned long long*)out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -347,7 +322,7 @@ int pp_graph_triad_entry_counts(const int64_t* row_ptr, const int64_t* row, cons
                                 int group, int64_t heavy_min, int64_t* cnt, void* ws, size_t ws_bytes, pp_stream_t stream) {
     using namespace pp;
     PP_REQUIRE(n >= 0 && ms >= 0 && 0 <= e0 && e0 <= e1 && e1 <= ms, PP_ERR_ARG, "pp_graph_triad_entry_counts: bad sizes");
-    PP_REQUIRE(width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_triad_entry_counts: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_triad_entry_counts: group must be 0 or a power of two up to 64");
     PP_REQUIRE(e1 == e0 || (row_ptr && row && col && cnt), PP_ERR_ARG, "pp_graph_triad_entry_counts: null argument");
     PP_REQUIRE(ws_bytes >= pp_graph_meet_ws_bytes(e1 - e0), PP_ERR_WORKSPACE, "pp_graph_triad_entry_counts: workspace too small");
     const TriadWs w = carve_triads(ws, e1 - e0, false);
@@ -355,7 +330,7 @@ int pp_graph_triad_entry_counts(const int64_t* row_ptr, const int64_t* row, cons
     a.row_ptr = row_ptr; a.col = col; a.n = n; a.ms = ms;
     a.first = col + e0; a.second = row + e0; a.tasks = e1 - e0;
     a.common = cnt; a.heavy_list = w.heavy_list; a.heavy_count = w.heavy_count;
-    return run_meet(a, pick_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMin, (hipStream_t)stream);
+    return run_meet(a, row_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMinDefault, (hipStream_t)stream);
 }
 
 size_t pp_graph_triad_node_counts_ws_bytes(int64_t ms) { return pp::carve_triads(nullptr, ms > 0 ? ms : 0, true).total; }
@@ -364,7 +339,7 @@ int pp_graph_triad_node_counts(const int64_t* row_ptr, const int64_t* row, const
                                int64_t* triads, void* ws, size_t ws_bytes, pp_stream_t stream) {
     using namespace pp;
     PP_REQUIRE(n >= 0 && ms >= 0, PP_ERR_ARG, "pp_graph_triad_node_counts: negative size");
-    PP_REQUIRE(width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_triad_node_counts: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_triad_node_counts: group must be 0 or a power of two up to 64");
     PP_REQUIRE(n == 0 || (row_ptr && triads), PP_ERR_ARG, "pp_graph_triad_node_counts: null argument");
     PP_REQUIRE(ms == 0 || (row && col), PP_ERR_ARG, "pp_graph_triad_node_counts: null argument");
     PP_REQUIRE(ws_bytes >= pp_graph_triad_node_counts_ws_bytes(ms), PP_ERR_WORKSPACE, "pp_graph_triad_node_counts: workspace too small");
@@ -375,11 +350,11 @@ int pp_graph_triad_node_counts(const int64_t* row_ptr, const int64_t* row, const
     a.row_ptr = row_ptr; a.col = col; a.n = n; a.ms = ms;
     a.first = col; a.second = row; a.tasks = ms;
     a.common = w.cnt; a.heavy_list = w.heavy_list; a.heavy_count = w.heavy_count;
-    int rc = run_meet(a, pick_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMin, st);
+    int rc = run_meet(a, row_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMinDefault, st);
     if (rc != PP_OK) return rc;
     rc = exclusive_scan<int64_t, int64_t>(w.cnt, ms, w.scan, true, nullptr, w.scan_ws, w.scan_bytes, st);
     if (rc != PP_OK) return rc;
-    k_row_totals<<<triad_grid(n, kBlock), kBlock, 0, st>>>(row_ptr, w.scan, n, ms, triads);
+    k_row_totals<<<capped_grid(n, kBlock), kBlock, 0, st>>>(row_ptr, w.scan, n, ms, triads);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -389,7 +364,7 @@ int pp_graph_pair_meets(const int64_t* row_ptr, const int64_t* col, const int64_
                         int64_t* dot, double* aa, int64_t* sizes, void* ws, size_t ws_bytes, pp_stream_t stream) {
     using namespace pp;
     PP_REQUIRE(n >= 0 && ms >= 0 && P >= 0 && table_len >= 0, PP_ERR_ARG, "pp_graph_pair_meets: negative size");
-    PP_REQUIRE(width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_pair_meets: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_pair_meets: group must be 0 or a power of two up to 64");
     PP_REQUIRE(P == 0 || (pairs && common && (n == 0 || row_ptr) && (ms == 0 || col)), PP_ERR_ARG, "pp_graph_pair_meets: null argument");
     PP_REQUIRE(!aa || (table && deg_ptr && table_len >= 1), PP_ERR_ARG, "pp_graph_pair_meets: aa needs the table and the stored row pointers");
     PP_REQUIRE(ws_bytes >= pp_graph_meet_ws_bytes(P), PP_ERR_WORKSPACE, "pp_graph_pair_meets: workspace too small");
@@ -400,7 +375,7 @@ int pp_graph_pair_meets(const int64_t* row_ptr, const int64_t* col, const int64_
     a.deg_ptr = deg_ptr; a.table = aa ? table : nullptr; a.table_len = table_len;
     a.common = common; a.dot = dot; a.aa = aa; a.sizes = sizes;
     a.heavy_list = w.heavy_list; a.heavy_count = w.heavy_count;
-    return run_meet(a, pick_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMin, (hipStream_t)stream);
+    return run_meet(a, row_width(group, n, ms), heavy_min > 0 ? heavy_min : kHeavyMinDefault, (hipStream_t)stream);
 }
 
 int pp_pair_measure(int measure, const int64_t* common, const int64_t* dot, const double* aa, const int64_t* sizes, const int64_t* norm2,
@@ -413,7 +388,7 @@ int pp_pair_measure(int measure, const int64_t* common, const int64_t* dot, cons
     PP_REQUIRE((measure != PP_PAIR_OVERLAP && measure != PP_PAIR_JACCARD) || sizes, PP_ERR_ARG, "pp_pair_measure: the list lengths are required");
     PP_REQUIRE(measure != PP_PAIR_ADAMIC_ADAR || aa, PP_ERR_ARG, "pp_pair_measure: aa is required");
     PP_REQUIRE(measure != PP_PAIR_COSINE || (dot && norm2 && indeg && pairs), PP_ERR_ARG, "pp_pair_measure: cosine needs dot, norm2, indeg and pairs");
-    k_pair_measure<<<triad_grid(P, kBlock), kBlock, 0, (hipStream_t)stream>>>(measure, common, dot, aa, sizes, norm2, indeg, pairs, P, n, out);
+    k_pair_measure<<<capped_grid(P, kBlock), kBlock, 0, (hipStream_t)stream>>>(measure, common, dot, aa, sizes, norm2, indeg, pairs, P, n, out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -427,7 +402,7 @@ int pp_graph_triad_fill(const int64_t* row_ptr, const int64_t* col, int64_t n, i
     if (total == 0 || ms == 0) return PP_OK;
     MeetArgs a{};
     a.row_ptr = row_ptr; a.col = col; a.n = n; a.ms = ms;
-    k_triad_fill<<<triad_grid(ms, kWavesPerBlock), kBlock, 0, (hipStream_t)stream>>>(a, v, offset, offsets, total, out);
+    k_triad_fill<<<capped_grid(ms, kWavesPerBlock), kBlock, 0, (hipStream_t)stream>>>(a, v, offset, offsets, total, out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -438,7 +413,7 @@ int pp_degree_product_sum(const int64_t* edge_index, int64_t m, int64_t n, const
     hipStream_t st = (hipStream_t)stream;
     PP_HIP(hipMemsetAsync(out, 0, sizeof(int64_t), st));
     if (m == 0) return PP_OK;
-    k_degree_products<<<triad_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, n, a, b, (unsigned long long*)out);
+    k_degree_products<<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, m, n, a, b, (unsigned long long*)out);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }

@@ -16,7 +16,7 @@
 //                Different: it stays unresolved and takes part in the group's next election.  Passes repeat until nobody is unresolved — one
 //                pass with a working hash, more with mask = 0, the exact classes either way.
 //   5. numbers : the elected nodes are flagged at their rank, the flags are scanned, a node's new colour is the scan at its class's rank.
-// Work split of 2 and 4 (as pp_graph_triads.hip): a row belongs to a GROUP of `width` lanes (a power of two, 1 .. 64, chosen from the mean
+// Work split of 2 and 4 (pp_rows.h): a row belongs to a GROUP of `width` lanes (a power of two, 1 .. 64, chosen from the mean
 // degree); a row of heavy_min entries or more is left to a second launch with a whole workgroup per row.  The list of heavy rows is made
 // once; its order depends on scheduling, no output does: every node writes its own words, elections are integer atomicMin, sums are integer.
 // The round loop is a HOST loop over launches (as in pp_graph_components.hip) with one read-back per verify pass: {unresolved, classes}.
@@ -25,25 +25,9 @@
 
 #include "pp_common.h"
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
-
-constexpr int64_t kWlHeavyMin = 1024;
-
-static inline unsigned wl_grid(int64_t items, int64_t per_block) {
-    int64_t g = ceil_div(items > 0 ? items : 1, per_block);
-    return (unsigned)(g > kMaxGrid ? kMaxGrid : g);
-}
-
-// width: the smallest power of two that is no less than the mean degree, between 4 and a wave (pick_width of pp_graph_triads.hip)
-static int wl_width(int group, int64_t n, int64_t m) {
-    if (group > 0) return group;
-    const int64_t mean = n > 0 ? ceil_div(m, n) : 1;
-    int w = 4;
-    while (w < kWave && w < mean) w <<= 1;
-    return w;
-}
-static bool wl_width_ok(int group) { return group == 0 || (group >= 1 && group <= kWave && (group & (group - 1)) == 0); }
 
 struct WlArgs {
     const int64_t* row_ptr;        // [n + 1]
@@ -61,14 +45,6 @@ struct WlArgs {
     int64_t heavy_count, heavy_min;
     int trust;                     // verify without comparing: the groups are exact already (round 0: groups of equal initial colour)
 };
-
-__device__ __forceinline__ void wl_bounds(const WlArgs& a, int64_t v, int64_t& lo, int64_t& hi) {
-    int64_t p = a.row_ptr[v], q = a.row_ptr[v + 1];
-    p = p < 0 ? 0 : (p > a.m ? a.m : p);
-    q = q > a.m ? a.m : q;                                                              // (a row pointer is never trusted past the entry array)
-    lo = p;
-    hi = q < p ? p : q;
-}
 
 __device__ __forceinline__ uint64_t wl_mix1(uint64_t x) {                               // (the finaliser of splitmix64)
     x += 0x9E3779B97F4A7C15ull;
@@ -134,14 +110,11 @@ __global__ __launch_bounds__(kBlock) void k_wl_sig_groups(WlArgs a, int width) {
         int64_t lo = 0, hi = 0;
         bool heavy = false;
         if (live) {
-            wl_bounds(a, v, lo, hi);
+            row_span(a.row_ptr, v, a.m, lo, hi);
             heavy = hi - lo >= a.heavy_min;
             if (!heavy) wl_hash_row(a, v, lo, hi, sub, width, h1, h2);
         }
-        for (int d = width >> 1; d > 0; d >>= 1) {                                      // (partners share the node: both are here)
-            h1 += (uint64_t)__shfl_xor((unsigned long long)h1, d, kWave);
-            h2 += (uint64_t)__shfl_xor((unsigned long long)h2, d, kWave);
-        }
+        group_sum(width, h1, h2);                                                       // (partners share the node: both are here)
         if (live && sub == 0 && !heavy) wl_put_sig(a, v, hi - lo, h1, h2);
     }
 }
@@ -152,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void k_wl_sig_blocks(WlArgs a) {
         const int64_t v = a.heavy_list[i];
         if ((uint64_t)v >= (uint64_t)a.n) continue;                                     // (uniform in the workgroup)
         int64_t lo, hi;
-        wl_bounds(a, v, lo, hi);
+        row_span(a.row_ptr, v, a.m, lo, hi);
         uint64_t h1 = 0, h2 = 0;
         wl_hash_row(a, v, lo, hi, (int)threadIdx.x, kBlock, h1, h2);
         h1 = wave_sum((unsigned long long)h1);
@@ -187,7 +160,7 @@ __global__ __launch_bounds__(kBlock) void k_wl_verify_groups(WlArgs a, int width
         int64_t lo = 0, hi = 0, r = -1;
         bool todo = v < a.n && a.class_rep[v] < 0, differ = false;
         if (todo) {
-            wl_bounds(a, v, lo, hi);
+            row_span(a.row_ptr, v, a.m, lo, hi);
             todo = hi - lo < a.heavy_min;
         }
         if (todo) {
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void k_wl_verify_groups(WlArgs a, int width
             if (r < 0) differ = true;
             else if (r != v && !a.trust) {
                 int64_t rlo, rhi;
-                wl_bounds(a, r, rlo, rhi);
+                row_span(a.row_ptr, r, a.m, rlo, rhi);
                 differ = a.colour[r] != a.colour[v] || rhi - rlo != hi - lo || wl_rows_differ(a, v, lo, hi, r, rlo, sub, width);
             }
         }
@@ -213,13 +186,13 @@ __global__ __launch_bounds__(kBlock) void k_wl_verify_blocks(WlArgs a) {
         if (threadIdx.x == 0) s_bad = 0;
         __syncthreads();
         int64_t lo, hi;
-        wl_bounds(a, v, lo, hi);
+        row_span(a.row_ptr, v, a.m, lo, hi);
         const int64_t r = wl_elected(a, v);
         bool differ = false;
         if (r < 0) differ = true;
         else if (r != v && !a.trust) {
             int64_t rlo, rhi;
-            wl_bounds(a, r, rlo, rhi);
+            row_span(a.row_ptr, r, a.m, rlo, rhi);
             differ = a.colour[r] != a.colour[v] || rhi - rlo != hi - lo || wl_rows_differ(a, v, lo, hi, r, rlo, (int)threadIdx.x, kBlock);
         }
         if (differ) s_bad = 1;
@@ -273,10 +246,9 @@ __global__ __launch_bounds__(kBlock) void k_wl_entry_rows(const int64_t* __restr
 __global__ __launch_bounds__(kBlock) void k_wl_heavy_rows(const int64_t* __restrict__ row_ptr, int64_t n, int64_t m, int64_t heavy_min,
                                                          uint32_t* __restrict__ heavy_list, int64_t* results) {
     for (int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x; v < n; v += (int64_t)gridDim.x * kBlock) {
-        int64_t p = row_ptr[v], q = row_ptr[v + 1];
-        p = p < 0 ? 0 : (p > m ? m : p);
-        q = q > m ? m : (q < p ? p : q);
-        if (q - p >= heavy_min) heavy_list[atomicAdd((unsigned long long*)&results[3], 1ull)] = (uint32_t)v;        // (each node at most once: n entries)
+        int64_t lo, hi;
+        row_span(row_ptr, v, m, lo, hi);
+        if (hi - lo >= heavy_min) heavy_list[atomicAdd((unsigned long long*)&results[3], 1ull)] = (uint32_t)v;        // (each node at most once: n entries)
     }
 }
 
@@ -351,7 +323,7 @@ struct WlClock {
 // elect, verify, number until nobody is unresolved; `colour_out` and host[1] = the class count are valid when it returns PP_OK
 static int wl_resolve_classes(WlArgs& a, const WlWs& w, int width, int64_t* colour_out, int64_t* host, int64_t* passes, hipStream_t st) {
     const int64_t n = a.n;
-    const unsigned gn = wl_grid(n, kBlock);
+    const unsigned gn = capped_grid(n, kBlock);
     PP_HIP(hipMemsetAsync(w.class_rep, 0xff, (size_t)n * sizeof(int32_t), st));         // -1: unresolved
     *passes = 0;
     for (;;) {
@@ -361,10 +333,10 @@ static int wl_resolve_classes(WlArgs& a, const WlWs& w, int width, int64_t* colo
         PP_HIP(hipMemsetAsync(w.rep_rank, 0xff, (size_t)n * sizeof(uint32_t), st));
         k_wl_elect<<<gn, kBlock, 0, st>>>(w.group, w.rank, w.class_rep, n, w.rep_rank);
         PP_LAUNCH_CHECK();
-        k_wl_verify_groups<<<wl_grid(n, kBlock / width), kBlock, 0, st>>>(a, width);
+        k_wl_verify_groups<<<capped_grid(n, kBlock / width), kBlock, 0, st>>>(a, width);
         PP_LAUNCH_CHECK();
         if (a.heavy_count > 0) {
-            k_wl_verify_blocks<<<wl_grid(a.heavy_count, 1), kBlock, 0, st>>>(a);
+            k_wl_verify_blocks<<<capped_grid(a.heavy_count, 1), kBlock, 0, st>>>(a);
             PP_LAUNCH_CHECK();
         }
         const int rc = exclusive_scan<int32_t, int32_t>(w.flag, n, w.pos, true, w.results + 1, w.scan, w.scan_bytes, st);
@@ -381,7 +353,7 @@ static int wl_resolve_classes(WlArgs& a, const WlWs& w, int width, int64_t* colo
 
 extern "C" {
 
-int64_t pp_graph_wl_heavy_min(void) { return pp::kWlHeavyMin; }
+int64_t pp_graph_wl_heavy_min(void) { return pp::kHeavyMinDefault; }
 
 size_t pp_graph_wl_ws_bytes(int64_t n, int64_t m) { return pp::carve_wl(nullptr, n > 0 ? n : 0, m > 0 ? m : 0).total; }
 
@@ -394,7 +366,7 @@ int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, in
     PP_REQUIRE(counts && passes && rounds_out && stats_cap >= 2, PP_ERR_ARG, "pp_graph_wl_refine: counts, passes (two entries or more) and rounds_out are required");
     PP_REQUIRE(n == 0 || (colours && row_ptr), PP_ERR_ARG, "pp_graph_wl_refine: colours and row_ptr are required");
     PP_REQUIRE(m == 0 || col, PP_ERR_ARG, "pp_graph_wl_refine: col is required");
-    PP_REQUIRE(wl_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_wl_refine: group must be 0 or a power of two up to 64");
+    PP_REQUIRE(row_width_ok(group) && heavy_min >= 0, PP_ERR_ARG, "pp_graph_wl_refine: group must be 0 or a power of two up to 64");
     PP_REQUIRE(ws_bytes >= pp_graph_wl_ws_bytes(n, m), PP_ERR_WORKSPACE, "pp_graph_wl_refine: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     if (seconds) seconds[0] = seconds[1] = seconds[2] = 0.0;
@@ -405,8 +377,8 @@ int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, in
         return PP_OK;
     }
     const WlWs w = carve_wl(ws, n, m);
-    const int width = wl_width(group, n, m);
-    const unsigned gn = wl_grid(n, kBlock), gm = wl_grid(m, kBlock);
+    const int width = row_width(group, n, m);
+    const unsigned gn = capped_grid(n, kBlock), gm = capped_grid(m, kBlock);
     int64_t host[4] = {0, 0, 0, 0};
     WlClock clock{seconds, st, {}};
 
@@ -422,7 +394,7 @@ int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, in
     WlArgs a{};
     a.row_ptr = row_ptr; a.sorted = w.sorted; a.n = n; a.m = m; a.mask = (uint64_t)hash_mask; a.sig = w.sig; a.group = w.group;
     a.rank = w.rank; a.node_of_rank = w.node_of_rank; a.rep_rank = w.rep_rank; a.class_rep = w.class_rep; a.flag = w.flag;
-    a.results = w.results; a.heavy_list = w.heavy_list; a.heavy_min = heavy_min > 0 ? heavy_min : kWlHeavyMin;
+    a.results = w.results; a.heavy_list = w.heavy_list; a.heavy_min = heavy_min > 0 ? heavy_min : kHeavyMinDefault;
     if (m > 0) {
         k_wl_entry_rows<<<gm, kBlock, 0, st>>>(row_ptr, n, m, w.row_of);
         PP_LAUNCH_CHECK();
@@ -478,10 +450,10 @@ int pp_graph_wl_refine(const int64_t* row_ptr, const int64_t* col, int64_t n, in
             if (rc != PP_OK) return rc;
         }
         if ((rc = clock.stop(0)) != PP_OK || (rc = clock.start()) != PP_OK) return rc;
-        k_wl_sig_groups<<<wl_grid(n, kBlock / width), kBlock, 0, st>>>(a, width);
+        k_wl_sig_groups<<<capped_grid(n, kBlock / width), kBlock, 0, st>>>(a, width);
         PP_LAUNCH_CHECK();
         if (a.heavy_count > 0) {
-            k_wl_sig_blocks<<<wl_grid(a.heavy_count, 1), kBlock, 0, st>>>(a);
+            k_wl_sig_blocks<<<capped_grid(a.heavy_count, 1), kBlock, 0, st>>>(a);
             PP_LAUNCH_CHECK();
         }
         if ((rc = clock.stop(1)) != PP_OK || (rc = clock.start()) != PP_OK) return rc;

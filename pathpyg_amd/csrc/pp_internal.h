@@ -37,6 +37,12 @@ template <typename IdxT>
 int histogram(const IdxT* idx, int64_t n, int64_t nbins, int32_t* bins, hipStream_t st);
 int minmax_i64(const int64_t* a, int64_t n, int64_t* out2, hipStream_t st);
 
+// pp_rows.hip
+// list[0 .. count) = the rows of `ptr` ([n + 1], entries clamped into [0, total]) with heavy_min entries or more, ASCENDING; the count goes
+// to the device word `count_dev`.  flag [n], pos [n + 1] and list [n] are the caller's; the scan workspace holds scan_ws_bytes(n).
+int heavy_rows_ascending(const int64_t* ptr, int64_t n, int64_t total, int64_t heavy_min, int32_t* flag, int32_t* pos, int32_t* list,
+                         int64_t* count_dev, void* scan_ws, size_t scan_bytes, hipStream_t st);
+
 // pp_sort.hip
 size_t sort_ws_bytes(int64_t n, int key_bytes);
 // Stable LSD radix sort of (key, value) pairs on key bits [begin_bit, end_bit).

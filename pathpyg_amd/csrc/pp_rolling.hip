@@ -23,6 +23,7 @@
 // to a group whose edges fit a budget.  lo / hi are read at random by every thread: they are staged in LDS while the group has at most
 // kRollLdsWindows windows and are left to the caches beyond that.
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
 
@@ -201,11 +202,6 @@ __global__ __launch_bounds__(kEmitBlock) void k_roll_emit(const KeyT* __restrict
 
 static inline int roll_bits(int64_t num_nodes) { return bits_for((uint64_t)(num_nodes > 1 ? num_nodes - 1 : 1)); }
 
-static inline int roll_grid(int64_t n) {
-    int64_t g = ceil_div(n, kBlock);
-    return (int)(g > kMaxGrid ? kMaxGrid : (g < 1 ? 1 : g));
-}
-
 template <typename KeyT, typename TimeT>
 static int rolling_group(const int64_t* edge_index, const TimeT* time, int64_t m, int64_t num_nodes, KeyT* keys_out, uint32_t* perm_out,
                          int32_t* flags, void* ws, size_t ws_bytes, hipStream_t st) {
@@ -213,7 +209,7 @@ static int rolling_group(const int64_t* edge_index, const TimeT* time, int64_t m
     Arena a(ws, ws_bytes);
     KeyT* raw = a.take<KeyT>(m);
     PP_REQUIRE(a.ok() && ws_bytes - a.used >= sort_ws_bytes(m, sizeof(KeyT)), PP_ERR_WORKSPACE, "pp_rolling_group: workspace too small");
-    k_roll_keys<KeyT, TimeT><<<roll_grid(m), kBlock, 0, st>>>(edge_index, edge_index + m, time, m, num_nodes, bits, raw, flags);
+    k_roll_keys<KeyT, TimeT><<<capped_grid(m, kBlock), kBlock, 0, st>>>(edge_index, edge_index + m, time, m, num_nodes, bits, raw, flags);
     PP_LAUNCH_CHECK();
     return sort_pairs<KeyT>(raw, nullptr, keys_out, perm_out, m, 0, 2 * bits, (char*)ws + a.used, ws_bytes - a.used, st);
 }
@@ -246,9 +242,9 @@ static int rolling_count(const KeyT* keys, const uint32_t* perm, int64_t m, cons
                          int64_t max_run, const int32_t* flags, int32_t* cnt, int32_t* report, hipStream_t st) {
     PP_HIP(hipMemsetAsync(report, 0, (size_t)(w1 - w0 + 2) * sizeof(int32_t), st));
     if (w1 - w0 <= kRollLdsWindows)
-        k_roll_count<KeyT, true><<<roll_grid(m), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, max_run, flags, cnt, report);
+        k_roll_count<KeyT, true><<<capped_grid(m, kBlock), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, max_run, flags, cnt, report);
     else
-        k_roll_count<KeyT, false><<<roll_grid(m), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, max_run, flags, cnt, report);
+        k_roll_count<KeyT, false><<<capped_grid(m, kBlock), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, max_run, flags, cnt, report);
     PP_LAUNCH_CHECK();
     return PP_OK;
 }
@@ -265,9 +261,9 @@ static int rolling_fill(const KeyT* keys, const uint32_t* perm, int64_t m, int b
     if (rc != PP_OK) return rc;
     // (`total` is the sum of `cnt`, so every slot is written; should a caller pass a larger one, k_roll_emit skips what lies outside [0, m) x [0, wn))
     if (wn <= kRollLdsWindows)
-        k_roll_fill<KeyT, true><<<roll_grid(m), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, w.ptr, total, w.wkey, w.pos);
+        k_roll_fill<KeyT, true><<<capped_grid(m, kBlock), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, w.ptr, total, w.wkey, w.pos);
     else
-        k_roll_fill<KeyT, false><<<roll_grid(m), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, w.ptr, total, w.wkey, w.pos);
+        k_roll_fill<KeyT, false><<<capped_grid(m, kBlock), kBlock, 0, st>>>(keys, perm, m, lo, hi, w0, w1, w.ptr, total, w.wkey, w.pos);
     PP_LAUNCH_CHECK();
     const uint32_t *wkey = w.wkey, *pos = w.pos;
     if (wn > 1) {      // one window: pair-major order is the window's order already

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "pp_internal.h"
+#include "pp_rows.h"
 
 namespace pp {
 namespace {
@@ -50,8 +51,9 @@ __device__ __forceinline__ int64_t wave_sat_sum(int64_t v, bool& sat) {
     return v;
 }
 
-// the workgroup's sum of one double per thread in a fixed shape: butterfly inside each wave, then the four waves left to right
-__device__ __forceinline__ double block_sum_fixed(double v, double* s4) {
+// the workgroup's sum of one double per thread in a fixed shape: butterfly inside each wave, then the four waves left to right, starting
+// from the first wave's word (pp_rows.h's block_sum_fixed starts from 0.0 and so differs on four partials of -0.0: keep them apart)
+__device__ __forceinline__ double block_sum_ltr(double v, double* s4) {
     v = wave_sum(v);
     __syncthreads();
     if (lane_id() == 0) s4[wave_id()] = v;
@@ -228,14 +230,14 @@ __global__ __launch_bounds__(kBlock) void k_rows_long(const void* ptr, int pw, i
         row_bounds(ptr, pw, r, total, lo, hi);
         double s = 0.0;
         for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock) s += (double)w[e];
-        s = block_sum_fixed(s, s4);
+        s = block_sum_ltr(s, s4);
         if (kTerms) {
             double t = 0.0;
             for (int64_t e = lo + threadIdx.x; e < hi; e += kBlock) {
                 const double x = (double)w[e];
                 t += x * log(x / s);
             }
-            s = block_sum_fixed(t, s4);
+            s = block_sum_ltr(t, s4);
         }
         if (threadIdx.x == 0) row_out[r] = s;
     }
@@ -290,7 +292,7 @@ struct VecStart {            // f_w log(c[first node of walk w] / P): :325-336
     }
 };
 
-// partial[c] = entries [c * kChunk, (c + 1) * kChunk): thread t adds its 8 strided entries in ascending order, then block_sum_fixed
+// partial[c] = entries [c * kChunk, (c + 1) * kChunk): thread t adds its 8 strided entries in ascending order, then block_sum_ltr
 template <typename F>
 __global__ __launch_bounds__(kBlock) void k_chunks(F f, int64_t n, double* __restrict__ partial, int64_t* status) {
     __shared__ double s4[kWavesPerBlock];
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(kBlock) void k_chunks(F f, int64_t n, double* __res
             const int64_t i = c * kChunk + (int64_t)j * kBlock + threadIdx.x;
             if (i < n) acc += f(i, st);
         }
-        acc = block_sum_fixed(acc, s4);
+        acc = block_sum_ltr(acc, s4);
         if (threadIdx.x == 0) partial[c] = acc;
     }
     if (st) atomicOr((unsigned long long*)status, (unsigned long long)st);
@@ -318,13 +320,13 @@ struct FinalJobs {
     FinalJob job[2];
 };
 
-// one workgroup per job adds the partial sums in index order (thread t: t, t + 256, ...), then block_sum_fixed
+// one workgroup per job adds the partial sums in index order (thread t: t, t + 256, ...), then block_sum_ltr
 __global__ __launch_bounds__(kBlock) void k_final(FinalJobs js) {
     __shared__ double s4[kWavesPerBlock];
     const FinalJob j = js.job[blockIdx.x];
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < j.count; i += kBlock) acc += j.partial[i];
-    acc = block_sum_fixed(acc, s4);
+    acc = block_sum_ltr(acc, s4);
     if (threadIdx.x == 0) *j.out = acc;
 }
 
@@ -332,10 +334,6 @@ static inline int64_t chunks_of(int64_t n) { return ceil_div(n > 0 ? n : 1, kChu
 static inline unsigned chunk_grid(int64_t n) {
     const int64_t c = chunks_of(n);
     return (unsigned)(c > kMaxGrid ? kMaxGrid : c);
-}
-static inline unsigned row_grid(int64_t rows) {
-    const int64_t g = ceil_div(rows > 0 ? rows : 1, kWavesPerBlock);
-    return (unsigned)(g > kMaxGrid ? kMaxGrid : g);
 }
 static inline int64_t long_cap(int64_t entries) { return entries / kLongRow + 1; }
 static inline unsigned long_grid(int64_t entries) {
@@ -482,7 +480,7 @@ int pp_walk_counts_i64(const void* row_ptr, int ptr_wide, const void* col, int c
         int64_t* cur = c[k & 1];
         if (k > 0) {
             const int64_t* prev = c[(k - 1) & 1];
-            k_walk_step<<<row_grid(n), kBlock, 0, st>>>(row_ptr, ptr_wide, col, col_wide, n, n_edges, prev, cur, sat + k, status);
+            k_walk_step<<<capped_grid(n, kWavesPerBlock), kBlock, 0, st>>>(row_ptr, ptr_wide, col, col_wide, n, n_edges, prev, cur, sat + k, status);
             PP_LAUNCH_CHECK();
             if (n_edges > kLongRow) {
                 k_walk_step_long<<<long_grid(n_edges), kBlock, 0, st>>>(row_ptr, ptr_wide, col, col_wide, n, n_edges, prev, cur, long_rows, long_count,
@@ -516,7 +514,7 @@ int pp_mon_layer_llh_f64(const void* row_ptr, int ptr_wide, int64_t n_rows, cons
     FinalJobs js{};
     int jobs = 0;
     if (n_rows > 0) {
-        k_rows<true><<<row_grid(n_rows), kBlock, 0, st>>>(row_ptr, ptr_wide, n_rows, n_edges, weight, l.row_term, l.long_rows, l.long_count, (int32_t)long_cap(n_edges), status);
+        k_rows<true><<<capped_grid(n_rows, kWavesPerBlock), kBlock, 0, st>>>(row_ptr, ptr_wide, n_rows, n_edges, weight, l.row_term, l.long_rows, l.long_count, (int32_t)long_cap(n_edges), status);
         PP_LAUNCH_CHECK();
         if (n_edges > kLongRow) {
             k_rows_long<true><<<long_grid(n_edges), kBlock, 0, st>>>(row_ptr, ptr_wide, n_edges, weight, l.row_term, l.long_rows, l.long_count, (int32_t)long_cap(n_edges));
@@ -571,7 +569,7 @@ int pp_mon_zeroth_llh_f64(const int64_t* node_sequence, int64_t positions, const
     k_zero_weights<<<(unsigned)g, kBlock, 0, st>>>(z.pos_sorted, positions, z.offs, walks, dag_weight, z.w_sorted, status);
     PP_LAUNCH_CHECK();
     // C_v = float64 sum of the walk weights over the positions at v, then sum C
-    k_rows<false><<<row_grid(n), kBlock, 0, st>>>(z.nptr, 0, n, positions, z.w_sorted, z.row_sum, z.long_rows, z.long_count, (int32_t)long_cap(positions), status);
+    k_rows<false><<<capped_grid(n, kWavesPerBlock), kBlock, 0, st>>>(z.nptr, 0, n, positions, z.w_sorted, z.row_sum, z.long_rows, z.long_count, (int32_t)long_cap(positions), status);
     PP_LAUNCH_CHECK();
     if (positions > kLongRow) {
         k_rows_long<false><<<long_grid(positions), kBlock, 0, st>>>(z.nptr, 0, positions, z.w_sorted, z.row_sum, z.long_rows, z.long_count, (int32_t)long_cap(positions));
