@@ -30,10 +30,12 @@ constexpr int kGcnWaves = kGcnThreads / kWave;
 // the matrix pipe of a SIMD do not overlap across waves, tools/probes/mfma/overlap.hip, so the gather's VALU instructions are paid in
 // full).  Per tile ONE coalesced load each brings the 17 row pointers, the 16 self coefficients (both one tile ahead) and the first 4 and
 // the next 4 (index, value) pairs of all 16 rows (lane 4*row + slot); the lane groups take them with ds_bpermute.  Rows with more than 8
-// neighbours continue chunk-wise.
-template <int P, bool kHeavy, int kBatchOverride = 0>
+// neighbours continue chunk-wise.  kSwz (64-wide rows): the LDS tile has NO row padding (stride P); the 16-byte unit u of tile row r sits at
+// unit u ^ r instead, which keeps both the row-wise stores here and the column-wise reads of the MFMA stage free of bank conflicts.
+template <int P, bool kHeavy, int kBatchOverride = 0, bool kSwz = false>
 struct TileGather {
-    static constexpr int kLanes = P / 4, kGroups = kWave / kLanes, kRows = 16 / kGroups, TS = P + 4;
+    static_assert(!kSwz || P == 64, "the swizzled tile is the 64-wide one: 16 units per row, 16 rows");
+    static constexpr int kLanes = P / 4, kGroups = kWave / kLanes, kRows = 16 / kGroups, TS = kSwz ? P : P + 4;
     static constexpr int kBatch = kBatchOverride > 0 ? kBatchOverride : (kRows < 2 ? kRows : (kRows >= 8 ? 4 : 2));      // 128-wide rows: registers to spare for a deeper gather
     static constexpr int kShift = P == 16 ? 6 : (P == 32 ? 7 : (P == 64 ? 8 : 9));      // log2(row bytes)
     buf_t rs_x, rs_ptr, rs_self, rs_slot;
@@ -176,7 +178,7 @@ struct TileGather {
                     const float4 h = *(const float4*)(heavy.sum + (int64_t)hs * P + 4 * l);
                     acc[qq].x += h.x; acc[qq].y += h.y; acc[qq].z += h.z; acc[qq].w += h.w;
                 }
-                *(float4*)(tile + (g * kRows + q) * TS + 4 * l) = acc[qq];
+                *(float4*)(tile + (g * kRows + q) * TS + 4 * (kSwz ? (l ^ (g * kRows + q)) : l)) = acc[qq];
                 if (agg_out != nullptr && r < n_rows) store_row_f4(agg_out + r * P + 4 * l, acc[qq], n_rows * (int64_t)(P * 4) >= kStreamFromBytes);
             }
         }
@@ -202,9 +204,52 @@ struct TileGather {
 #ifndef PP_XCD_TILES
 #define PP_XCD_TILES 1          // every XCD sweeps a contiguous eighth of the tiles (0: the plain round-robin order, kept for A/B measurements)
 #endif
+// ---- The 64x64 layer product on split-bf16 MFMAs (PP_FWD_SPLIT, 0: the fp32 instructions everywhere, kept for A/B measurements).
+// An fp32 value is EXACTLY hi + mid + lo with three bf16 values, taken by truncation (hi = x & 0xffff0000, r = x - hi, mid = r & 0xffff0000,
+// lo = r - mid: every step exact, and hi never rounds up to infinity).  tile . W^T keeps the six largest of the nine cross products
+// (lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, accumulated in this order, smallest first), the dropped ones are below 2^-24 of |a||w|:
+// 2 k-blocks x 6 x 4 column tiles = 48 v_mfma_f32_16x16x32_bf16 (16 cycles each) instead of 64 v_mfma_f32_16x16x4_f32 (32 cycles each).
+// The exponent window: a tile (and W) takes the split only if each of its values is +-0 or 2^-40 <= |x| < 2^60.  Above 2^-40 the lowest
+// bit of lo (2^-23 of x) and every kept product (down to 2^-46 |a||w| >= 2^-126) is a normal number, so no bf16 or fp32 subnormal is ever
+// formed or flushed; below 2^60 a row's 64 products stay under 64 * 2^120 = 2^126 whichever way they are grouped, so the split sums
+// overflow exactly where the fp32 ones do: nowhere.  Non-finite values have the exponent field 255 and fall outside as well.  Everything
+// outside the window runs the fp32 instructions of before on the same operands (bit-identical to PP_FWD_SPLIT=0): a wave-uniform branch
+// per tile; W is tested once at staging, for the whole workgroup.
+// LDS: the three bf16 copies of W are 24 KB, [split][k-block][column tile][lane] x 8 bf16 = the B operand of one MFMA by one ds_read_b128
+// (lane (i, kq): W[CT*i + ct][16*kq + 8*kb + 0..7], the same (column, k) pairs the fp32 form gives this lane, so the epilogue is unchanged).
+// With them the padded wave tiles (17 KB) would make 4 workgroups 164 KB of the CU's 160 KB, so the tiles lose their padding for the XOR
+// swizzle of TileGather: 24 + 16 = 40 KB, 4 workgroups per CU as before.  There is no room for an fp32 W beside them: a tile outside the
+// window rebuilds its fp32 B values from the bf16 thirds (hi + (mid + lo) is exact), and a W outside the window is staged as fp32 INTO the
+// same buffer ([k-block][column tile][lane] x 8 floats, 16 KB) and every tile of the workgroup takes the fp32 path.
+#ifndef PP_FWD_SPLIT
+#define PP_FWD_SPLIT 1
+#endif
+using bf16x8 = __attribute__((__vector_size__(8 * sizeof(__bf16)))) __bf16;
+constexpr uint32_t kSplitLo = 87u << 23, kSplitHi = 187u << 23;        // |x| bit patterns of 2^-40 and 2^60
+
+__device__ __forceinline__ bool outside_split_window(uint32_t umax, uint32_t vmin) {      // umax = max |x| bits, vmin = min (|x| bits - 1): +-0 wraps to the top
+    return umax >= kSplitHi || vmin < kSplitLo - 1u;
+}
+
+// hi / mid / lo of two neighbouring fp32 values as packed bf16 pairs (the lower k in the low half)
+__device__ __forceinline__ void split_bf16x2(float x0, float x1, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
+    const uint32_t b0 = __float_as_uint(x0), b1 = __float_as_uint(x1);
+    hi = __builtin_amdgcn_perm(b1, b0, 0x07060302u);                   // (b0 >> 16) | (b1 & 0xffff0000)
+    const float r0 = x0 - __uint_as_float(b0 & 0xffff0000u), r1 = x1 - __uint_as_float(b1 & 0xffff0000u);
+    const uint32_t c0 = __float_as_uint(r0), c1 = __float_as_uint(r1);
+    mid = __builtin_amdgcn_perm(c1, c0, 0x07060302u);
+    const float l0 = r0 - __uint_as_float(c0 & 0xffff0000u), l1 = r1 - __uint_as_float(c1 & 0xffff0000u);
+    lo = __builtin_amdgcn_perm(__float_as_uint(l1), __float_as_uint(l0), 0x07060302u);
+}
+
+__device__ __forceinline__ f32x4 mfma_bf16(const uint32_t (&a)[4], uint4 b, f32x4 c) {
+    const uint4 av = make_uint4(a[0], a[1], a[2], a[3]);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
 template <int P, int Q, bool kHeavy, bool kWide, int kThreads = kGcnThreads, int kEpi = 0, bool kDrop = false>
 // (64 x 64: capped at 128 registers = 4 waves per SIMD — 126 VGPRs, no accumulator AGPRs, no spills; at the 146 registers the compiler
-// takes when left alone the kernel runs 3 waves per SIMD and the layer is 6 % slower: 1.77 -> 1.66 ms at 10^7 rows)
+// takes when left alone the kernel runs 3 waves per SIMD and the layer is 6 % slower: 1.77 -> 1.66 ms at 10^7 rows.  These are the numbers of
+// the PP_FWD_SPLIT=0 form; with the split product the plain kernel takes all 128, still without spills)
 __global__ __launch_bounds__(kThreads, (kThreads == 256 && P == 64 && Q == 64) ? PP_FWD_WAVES : 1) void k_gcn_forward(const int32_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                                                               const float* __restrict__ val, int64_t n_rows, const float* __restrict__ X,
                                                               const float* __restrict__ self_coef, const float* __restrict__ W,
@@ -212,20 +257,71 @@ __global__ __launch_bounds__(kThreads, (kThreads == 256 && P == 64 && Q == 64) ?
                                                               float* __restrict__ agg_out, float* __restrict__ Y,
                                                               const float* __restrict__ act_in, float* __restrict__ colsum, int64_t n_self,
                                                               DropSite drop) {
-    constexpr int kLanes = P / 4, kGroups = kWave / kLanes, kRows = 16 / kGroups, KQ = P / 4, CT = Q / 16, TS = P + 4;
+    constexpr bool kSplit = PP_FWD_SPLIT != 0 && kEpi == 0 && P == 64 && Q == 64 && kThreads == 256;      // the product on split-bf16 MFMAs (above)
+    constexpr int kLanes = P / 4, kGroups = kWave / kLanes, kRows = 16 / kGroups, KQ = P / 4, CT = Q / 16, TS = kSplit ? P : P + 4;
     constexpr int kBatch = kRows < 2 ? kRows : (kRows >= 8 ? 4 : 2);      // 128-wide rows: 2 waves/SIMD, registers to spare for a deeper gather
     constexpr int kWaves = kThreads / kWave;
     using off_t = typename std::conditional<kWide, uint64_t, uint32_t>::type;     // byte offset of a gathered row
-    __shared__ __attribute__((aligned(16))) float s_b[P * 16 * CT];
+    __shared__ __attribute__((aligned(16))) float s_b[kSplit ? 3 * 2 * CT * kWave * 4 : P * 16 * CT];
     __shared__ __attribute__((aligned(16))) float s_tile[kWaves][16 * TS];
-    // B[k][j] = W[j][k] (forward) or W[k][j] (input gradient), stored [k][j]: lane i of output tile ct works on column CT*i + ct, so that
-    // a lane ends up with CT CONSECUTIVE output columns per row (16-byte stores instead of 4-byte ones) and reads its CT B values at once
-    for (int e = threadIdx.x; e < P * Q; e += kThreads) {
-        if (kEpi == 0) {
-            const int j = e / P, k = e - j * P;
-            s_b[k * Q + j] = W[e];
-        } else {
-            s_b[e] = W[e];
+    [[maybe_unused]] bool w_fp32 = false;          // kSplit: W is outside the exponent window, the workgroup runs the fp32 instructions
+    if constexpr (kSplit) {
+        // a thread stages 8 consecutive k of one W row = one lane's share of one B operand: piece = (row j, k-block pair k8)
+        constexpr int kPieces = P * Q / 8 / kThreads;
+        float4 w[kPieces][2];
+        uint32_t umax = 0u, vmin = 0xffffffffu;
+#pragma unroll
+        for (int pc = 0; pc < kPieces; ++pc) {
+            const int piece = threadIdx.x + pc * kThreads;
+            const float* wp = W + piece * 8;                                           // (W is only known to be 4-byte aligned)
+            w[pc][0] = make_float4(wp[0], wp[1], wp[2], wp[3]);
+            w[pc][1] = make_float4(wp[4], wp[5], wp[6], wp[7]);
+            const float v[8] = {w[pc][0].x, w[pc][0].y, w[pc][0].z, w[pc][0].w, w[pc][1].x, w[pc][1].y, w[pc][1].z, w[pc][1].w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const uint32_t u = __float_as_uint(v[e]) & 0x7fffffffu;
+                umax = u > umax ? u : umax;
+                vmin = u - 1u < vmin ? u - 1u : vmin;
+            }
+        }
+        // (the workgroup-wide OR goes through a word of the tile buffer, idle until the first gather: __syncthreads_or() would take LDS of
+        // its own, and 4 workgroups fill the CU's 160 KB to the byte)
+        volatile int* flag = (volatile int*)&s_tile[0][0];
+        if (threadIdx.x == 0) *flag = 0;
+        __syncthreads();
+        if (outside_split_window(umax, vmin)) *flag = 1;
+        __syncthreads();
+        w_fp32 = __builtin_amdgcn_readfirstlane(*flag) != 0;
+#pragma unroll
+        for (int pc = 0; pc < kPieces; ++pc) {
+            const int piece = threadIdx.x + pc * kThreads;
+            const int j = piece >> 3, k8 = piece & 7;                                  // W[j][8*k8 ..]
+            const int slot = (((k8 & 1) * CT + (j & 3)) * kWave) + (k8 >> 1) * 16 + (j >> 2);     // [k-block][column tile][lane (i = j / CT, kq)]
+            if (w_fp32) {
+                *(float4*)(s_b + slot * 8) = w[pc][0];
+                *(float4*)(s_b + slot * 8 + 4) = w[pc][1];
+            } else {
+                uint4 hi, mid, lo;
+                split_bf16x2(w[pc][0].x, w[pc][0].y, hi.x, mid.x, lo.x);
+                split_bf16x2(w[pc][0].z, w[pc][0].w, hi.y, mid.y, lo.y);
+                split_bf16x2(w[pc][1].x, w[pc][1].y, hi.z, mid.z, lo.z);
+                split_bf16x2(w[pc][1].z, w[pc][1].w, hi.w, mid.w, lo.w);
+                uint4* sw = (uint4*)s_b;
+                sw[slot] = hi;
+                sw[2 * CT * kWave + slot] = mid;
+                sw[4 * CT * kWave + slot] = lo;
+            }
+        }
+    } else {
+        // B[k][j] = W[j][k] (forward) or W[k][j] (input gradient), stored [k][j]: lane i of output tile ct works on column CT*i + ct, so that
+        // a lane ends up with CT CONSECUTIVE output columns per row (16-byte stores instead of 4-byte ones) and reads its CT B values at once
+        for (int e = threadIdx.x; e < P * Q; e += kThreads) {
+            if (kEpi == 0) {
+                const int j = e / P, k = e - j * P;
+                s_b[k * Q + j] = W[e];
+            } else {
+                s_b[e] = W[e];
+            }
         }
     }
     __syncthreads();
@@ -262,7 +358,7 @@ __global__ __launch_bounds__(kThreads, (kThreads == 256 && P == 64 && Q == 64) ?
     // come by ONE coalesced load each (lane 4*row + slot) and are handed round with ds_bpermute; absent neighbours / rows past the end carry
     // the out-of-range offset and read as zeros.  The pointers are fetched one tile ahead.
     [[maybe_unused]] int p_next[kRows + 1];
-    [[maybe_unused]] TileGather<P, kHeavy> gather(X, ptr, idx, val, self_coef, heavy, n_rows, n_self);
+    [[maybe_unused]] TileGather<P, kHeavy, 0, kSplit> gather(X, ptr, idx, val, self_coef, heavy, n_rows, n_self);
     if constexpr (kWide) {
         {
             const int64_t t0 = tile_at(0);
@@ -367,7 +463,7 @@ __global__ __launch_bounds__(kThreads, (kThreads == 256 && P == 64 && Q == 64) ?
                         const float4 h = *(const float4*)(heavy.sum + (int64_t)hs[q] * P + 4 * l);
                         acc.x += h.x; acc.y += h.y; acc.z += h.z; acc.w += h.w;
                     }
-                    *(float4*)(tile + (g * kRows + q) * TS + 4 * l) = acc;
+                    *(float4*)(tile + (g * kRows + q) * TS + 4 * (kSplit ? (l ^ (g * kRows + q)) : l)) = acc;
                     if (agg_out != nullptr && r0 + q < n_rows) *(float4*)(agg_out + (r0 + q) * P + 4 * l) = acc;
                 }
             }
@@ -397,22 +493,94 @@ __global__ __launch_bounds__(kThreads, (kThreads == 256 && P == 64 && Q == 64) ?
         }
         float4 a[KQ / 4];
 #pragma unroll
-        for (int c = 0; c < KQ / 4; ++c) a[c] = *(const float4*)(tile + i * TS + kq * KQ + 4 * c);
+        for (int c = 0; c < KQ / 4; ++c) {
+            if constexpr (kSplit) {
+                int iv = i;                                // (opaque: the four swizzled addresses are rebuilt per tile, three XORs, instead of
+                asm volatile("" : "+v"(iv));               //  living in registers through the gather stage, which has none to spare)
+                a[c] = *(const float4*)(tile + i * TS + 4 * ((kq * (KQ / 4) + c) ^ iv));
+            } else {
+                a[c] = *(const float4*)(tile + i * TS + kq * KQ + 4 * c);
+            }
+        }
         f32x4 out[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) out[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
         __builtin_amdgcn_s_setprio(3);                    // a wave in its MFMA burst goes first: it frees the matrix pipe sooner (-2 %)
+        if constexpr (kSplit) {
+            bool split = !w_fp32;
+            if (split) {                                   // the tile's exponent window: one wave-uniform test
+                uint32_t umax = 0u, vmin = 0xffffffffu;
 #pragma unroll
-        for (int c = 0; c < KQ / 4; ++c) {
-            const float av[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
+                for (int c = 0; c < KQ / 4; ++c) {
+                    const float av[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float* bp = s_b + ((kq * KQ + 4 * c + e) * 16 + i) * CT;
-                float bv[CT];
+                    for (int e = 0; e < 4; ++e) {
+                        const uint32_t u = __float_as_uint(av[e]) & 0x7fffffffu;
+                        umax = u > umax ? u : umax;
+                        vmin = u - 1u < vmin ? u - 1u : vmin;
+                    }
+                }
+                split = __ballot(outside_split_window(umax, vmin)) == 0ull;
+            }
+            const uint4* sw = (const uint4*)s_b;
+            if (split) {
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) bv[ct] = bp[ct];
+                for (int kb = 0; kb < 2; ++kb) {
+                    uint32_t ah[4], am[4], al[4];
+                    split_bf16x2(a[2 * kb].x, a[2 * kb].y, ah[0], am[0], al[0]);
+                    split_bf16x2(a[2 * kb].z, a[2 * kb].w, ah[1], am[1], al[1]);
+                    split_bf16x2(a[2 * kb + 1].x, a[2 * kb + 1].y, ah[2], am[2], al[2]);
+                    split_bf16x2(a[2 * kb + 1].z, a[2 * kb + 1].w, ah[3], am[3], al[3]);
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) out[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[ct], out[ct], 0, 0, 0);
+                    for (int ct = 0; ct < CT; ++ct) {
+                        const int slot = (kb * CT + ct) * kWave + lane;
+                        const uint4 bh = sw[slot], bm = sw[2 * CT * kWave + slot], bl = sw[4 * CT * kWave + slot];
+                        out[ct] = mfma_bf16(al, bh, out[ct]);          // smallest first
+                        out[ct] = mfma_bf16(ah, bl, out[ct]);
+                        out[ct] = mfma_bf16(am, bm, out[ct]);
+                        out[ct] = mfma_bf16(am, bh, out[ct]);
+                        out[ct] = mfma_bf16(ah, bm, out[ct]);
+                        out[ct] = mfma_bf16(ah, bh, out[ct]);
+                    }
+                }
+            } else {                                       // the fp32 instructions, k ascending per accumulator as in the PP_FWD_SPLIT=0 form
+#pragma unroll
+                for (int kb = 0; kb < 2; ++kb) {
+                    const float av[8] = {a[2 * kb].x, a[2 * kb].y, a[2 * kb].z, a[2 * kb].w, a[2 * kb + 1].x, a[2 * kb + 1].y, a[2 * kb + 1].z, a[2 * kb + 1].w};
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) {
+                        const int slot = (kb * CT + ct) * kWave + lane;
+                        float bv[8];
+                        if (w_fp32) {
+                            const float4 b0 = *(const float4*)(s_b + slot * 8), b1 = *(const float4*)(s_b + slot * 8 + 4);
+                            bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
+                        } else {                           // W's thirds back to fp32: hi + (mid + lo), exact
+                            const uint4 bh = sw[slot], bm = sw[2 * CT * kWave + slot], bl = sw[4 * CT * kWave + slot];
+                            const uint32_t h[4] = {bh.x, bh.y, bh.z, bh.w}, m[4] = {bm.x, bm.y, bm.z, bm.w}, l3[4] = {bl.x, bl.y, bl.z, bl.w};
+#pragma unroll
+                            for (int pr = 0; pr < 4; ++pr) {
+                                bv[2 * pr] = __uint_as_float(h[pr] << 16) + (__uint_as_float(m[pr] << 16) + __uint_as_float(l3[pr] << 16));
+                                bv[2 * pr + 1] = __uint_as_float(h[pr] & 0xffff0000u) + (__uint_as_float(m[pr] & 0xffff0000u) + __uint_as_float(l3[pr] & 0xffff0000u));
+                            }
+                        }
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) out[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[e], out[ct], 0, 0, 0);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < KQ / 4; ++c) {
+                const float av[4] = {a[c].x, a[c].y, a[c].z, a[c].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float* bp = s_b + ((kq * KQ + 4 * c + e) * 16 + i) * CT;
+                    float bv[CT];
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) bv[ct] = bp[ct];
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) out[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], bv[ct], out[ct], 0, 0, 0);
+                }
             }
         }
         __builtin_amdgcn_s_setprio(0);
