@@ -1225,6 +1225,62 @@ int pp_graph_layout_adj_count(const int64_t* edge_index, int64_t m, int64_t n, i
 int pp_graph_layout_adj_fill(const double* weight, int64_t m, int64_t n, int64_t nnz, int64_t* ptr, int64_t* nbr, double* w, void* ws,
                              size_t ws_bytes, pp_stream_t stream);
 
+/* ------------------------------------------------------------------ random walks (pp_walks.hip) */
+/* Walks on a row-sorted CSR (row_ptr [n + 1], col [m] int64, device): a Graph, or a layer of a MultiOrderModel (no counterpart in the reference
+ * snapshot; upstream pathpyG samples in Python loops).  Every output is a pure function of (seed, graph, weights, arguments): the words are
+ * the Philox words of the random graph models above, under the tags below; the grid follows pp_set_launch_share and changes no bit.  No
+ * floating-point atomics.  A uniform is x(word) = (double)(word >> 11) * 2^-53.  All arithmetic is float64 and every operation named below
+ * is ONE rounded operation (nothing is contracted).  Pointers are clamped as everywhere (into [0, m], never descending).
+ * Sizes: n, m, walks, steps, order < 2^31 - 1 and walks * (steps + order) < 2^31 - 1, else PP_ERR_TOO_LARGE before any launch;
+ * pp_walk_check_sizes is that test alone (host code).
+ *
+ * pp_walk_table: weight [m] float32 or float64 (weight_dtype PP_F32 / PP_F64) widened to float64, NULL = all ones.  cum [m]: cum[j] = the
+ *   left-to-right running sum of the weights of j's row from the row's first entry to j (row-local: s = 0; s = s + w; one lane per row).
+ *   total [n]: T_v = the cum of v's last entry, 0 for an empty row.  bad [1] int32 (zeroed by the call) becomes 1 if a weight is negative,
+ *   NaN or infinite, or a T_v is infinite.
+ * pp_walk_start_table (start "weighted"): nodes in blocks of 1024 (pp_walk_start_blocks(n) of them).  bcum [n]: the left-to-right running sum
+ *   of T_v inside the node's block (one lane per block); block_cum [blocks] = B: the left-to-right running sum of the blocks' totals (the
+ *   bcum of each block's last node), by one lane.
+ * pp_walk_positive_flag / _list (start "uniform"): flag[v] = T_v > 0 (int32); with pos [n + 1] the exclusive scan of the flags and count =
+ *   pos[n], list [count] int32 = those nodes ascending.
+ * pp_walk_run: one lane per walk w, the step loop inside the kernel.  The start node is
+ *     start_mode 0: start_nodes[w] (int64; outside [0, n): the walk has no node, nodes[0][w] = -1, length 0);
+ *     start_mode 1: target = x(word(seed, PP_RG_TAG_WALK_START, stream 0, index w)) * B[last]; b = the first block with B[b] > target (the last
+ *       block if there is none); t2 = target - (b ? B[b - 1] : 0); the first node of block b with bcum > t2; if there is none (rounding), the
+ *       block's last node with T_v > 0;
+ *     start_mode 2: positive[d], d = the unbiased draw below positive_count by pp_rg_draws' rule (multiply-high, rejected while the low
+ *       product word is under 2^64 mod positive_count; attempt a reads the word of (PP_RG_TAG_WALK_START, stream a, index w)).
+ *   At step t = 0 .. steps - 1, at node v with entries [lo, hi): if the row is empty or not T_v > 0 the walk ends with length t (edges).
+ *   Otherwise target = x(word(seed, PP_RG_TAG_WALK_STEP, stream t, index w)) * T_v, j = the smallest index of [lo, hi) with cum[j] > target
+ *   (bisection bounded to the row) and the next node is col[j]; a column outside [0, n) ends the walk.  An entry of weight 0 is never chosen
+ *   (its cum equals its predecessor's, or is 0 at the row's start, and target >= 0).  target < T_v ALWAYS holds for a finite positive normal
+ *   T_v (x <= 1 - 2^-53, and x * T rounds below T), so the bound hi is never the answer; for a subnormal T_v where it could be, the walk ends.
+ *   nodes [steps + 1, walks] int32, STEP-MAJOR (a wave's stores at one step are contiguous), -1 after a walk's end; lengths [walks] int32.
+ *   `order` only enters the size test.
+ * pp_walk_pack_count / _fill: the walk store of PathData from the step-major buffer.  keep[w] = length > 0, count[w] = order + length where
+ *   kept, else 0 (int32).  With offset / rank [walks + 1] the exclusive scans of count / keep, positions = offset[walks], kept = rank[walks]
+ *   and node_sequence [n, order] int64 the graph's: seq_out [positions] int64 = per kept walk the `order` first-order nodes of its first
+ *   node, then the LAST first-order node of every later one; edge_src / edge_dst [positions - kept]: the chain p -> p + 1 inside every walk;
+ *   dag_num_nodes / dag_num_edges [kept] int64 = order + length, that minus one; dag_weight [kept] float32 = 1.  Walks without an edge are
+ *   left out. */
+#define PP_RG_TAG_WALK_START 10
+#define PP_RG_TAG_WALK_STEP 11
+int pp_walk_check_sizes(int64_t n, int64_t m, int64_t walks, int64_t steps, int64_t order);
+int pp_walk_table(const int64_t* row_ptr, int64_t n, int64_t m, const void* weight, int weight_dtype, double* cum, double* total, int32_t* bad,
+                  pp_stream_t stream);
+int64_t pp_walk_start_blocks(int64_t n);
+int pp_walk_start_table(const double* total, int64_t n, double* bcum, double* block_cum, pp_stream_t stream);
+int pp_walk_positive_flag(const double* total, int64_t n, int32_t* flag, pp_stream_t stream);
+int pp_walk_positive_list(const int64_t* pos, int64_t n, int64_t count, int32_t* list, pp_stream_t stream);
+int pp_walk_run(const int64_t* row_ptr, const int64_t* col, const double* cum, const double* total, int64_t n, int64_t m, int64_t walks, int64_t steps,
+                int64_t order, int64_t seed, int start_mode, const int64_t* start_nodes, const double* bcum, const double* block_cum,
+                const int32_t* positive, int64_t positive_count, int32_t* nodes, int32_t* lengths, pp_stream_t stream);
+int pp_walk_pack_count(const int32_t* lengths, int64_t walks, int64_t steps, int64_t order, int32_t* keep, int32_t* count, pp_stream_t stream);
+int pp_walk_pack_fill(const int32_t* nodes, const int32_t* lengths, int64_t walks, int64_t steps, int64_t order, int64_t n,
+                      const int64_t* node_sequence, const int64_t* offset, const int64_t* rank, int64_t positions, int64_t kept,
+                      int64_t* seq_out, int64_t* edge_src, int64_t* edge_dst, int64_t* dag_num_nodes, int64_t* dag_num_edges, float* dag_weight,
+                      pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3013,3 +3013,105 @@ def rg_mr_repair(edge_index: torch.Tensor, n: int, seed: int, round: int, multi:
             check(L.pp_rg_mr_swap(_p(flag), _p(claim), _p(sorted_k), k, n, _i64(seed), round, int(multi), edge_index[0].data_ptr(),
                                   edge_index[1].data_ptr(), _stream()), "pp_rg_mr_swap")
     return offenders
+
+
+# ------------------------------------------------------------------ random walks (csrc/pp_walks.hip)
+RG_TAG_WALK_START, RG_TAG_WALK_STEP = 10, 11                       # PP_RG_TAG_WALK_* of the header
+WALK_START_GIVEN, WALK_START_WEIGHTED, WALK_START_UNIFORM = 0, 1, 2
+
+
+def walk_check_sizes(n: int, m: int, walks: int, steps: int, order: int) -> None:
+    """The size limits of the walk kernels (host arithmetic, nothing is allocated): raises like the kernels would."""
+    check(lib().pp_walk_check_sizes(n, m, walks, steps, order), "pp_walk_check_sizes")
+
+
+class WalkTable(NamedTuple):
+    cum: torch.Tensor            # [m] float64: row-local running sums of the weights
+    total: torch.Tensor          # [n] float64: T_v
+    bad: bool                    # a weight was negative or not finite (or a row's sum overflowed)
+
+
+def walk_table(row_ptr: torch.Tensor, n: int, m: int, weight: torch.Tensor | None) -> WalkTable:
+    """The transition table of ``pp_walk_table``; one read-back (the flag)."""
+    dev = require_device(row_ptr, weight)
+    if weight is not None and weight.dtype not in (torch.float32, torch.float64):
+        raise TypeError("walk_table: float32 or float64 weights")
+    with torch.cuda.device(dev):
+        cum = torch.empty(m, dtype=torch.float64, device=dev)
+        total = torch.empty(n, dtype=torch.float64, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        code = _DTYPE_CODE[weight.dtype] if weight is not None else _DTYPE_CODE[torch.float64]
+        check(lib().pp_walk_table(_p(row_ptr), n, m, _p(weight), code, _p(cum), _p(total), _p(bad), _stream()), "pp_walk_table")
+        return WalkTable(cum, total, bool(bad.item()))
+
+
+def walk_start_table(total: torch.Tensor):
+    """``(bcum [n], B [blocks])`` of ``pp_walk_start_table``: running sums of T_v inside blocks of 1024 nodes, and of the blocks' totals."""
+    dev = require_device(total)
+    n = total.numel()
+    with torch.cuda.device(dev):
+        bcum = torch.empty(n, dtype=torch.float64, device=dev)
+        B = torch.empty(int(lib().pp_walk_start_blocks(n)), dtype=torch.float64, device=dev)
+        check(lib().pp_walk_start_table(_p(total), n, _p(bcum), _p(B), _stream()), "pp_walk_start_table")
+    return bcum, B
+
+
+def walk_positive_nodes(total: torch.Tensor) -> torch.Tensor:
+    """The nodes with T_v > 0, ascending (int32): flag -> scan -> compact, one read-back (their number)."""
+    dev = require_device(total)
+    n = total.numel()
+    with torch.cuda.device(dev):
+        flag = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib().pp_walk_positive_flag(_p(total), n, _p(flag), _stream()), "pp_walk_positive_flag")
+        pos = exclusive_scan(flag)
+        count = int(pos[-1].item())
+        out = torch.empty(count, dtype=torch.int32, device=dev)
+        check(lib().pp_walk_positive_list(_p(pos), n, count, _p(out), _stream()), "pp_walk_positive_list")
+    return out
+
+
+def walk_run(row_ptr: torch.Tensor, col: torch.Tensor, table: WalkTable, n: int, walks: int, steps: int, order: int, seed: int, mode: int,
+             start_nodes: torch.Tensor | None = None, start_table=None, positive: torch.Tensor | None = None):
+    """``(nodes [steps + 1, walks] int32 step-major, lengths [walks] int32)`` of ``pp_walk_run``."""
+    dev = require_device(row_ptr, col, table.cum, table.total, start_nodes, positive)
+    m = col.numel()
+    walk_check_sizes(n, m, walks, steps, order)
+    bcum, B = start_table if start_table is not None else (None, None)
+    with torch.cuda.device(dev):
+        nodes = torch.empty((steps + 1, walks), dtype=torch.int32, device=dev)
+        lengths = torch.empty(walks, dtype=torch.int32, device=dev)
+        check(lib().pp_walk_run(_p(row_ptr), _p(col), _p(table.cum), _p(table.total), n, m, walks, steps, order, _i64(seed), mode, _p(start_nodes),
+                                _p(bcum), _p(B), _p(positive), 0 if positive is None else positive.numel(), _p(nodes), _p(lengths), _stream()),
+              "pp_walk_run")
+    return nodes, lengths
+
+
+class WalkStore(NamedTuple):
+    node_sequence: torch.Tensor  # [P, 1] int64
+    edge_index: torch.Tensor     # [2, P - kept] int64
+    dag_num_nodes: torch.Tensor  # [kept] int64
+    dag_num_edges: torch.Tensor  # [kept] int64
+    dag_weight: torch.Tensor     # [kept] float32
+
+
+def walk_pack(nodes: torch.Tensor, lengths: torch.Tensor, node_sequence: torch.Tensor, n: int) -> WalkStore:
+    """The ``PathData`` tensors of a batch (``pp_walk_pack_count`` -> two scans -> ``pp_walk_pack_fill``); one read-back (the two totals)."""
+    dev = require_device(nodes, lengths, node_sequence)
+    steps, walks = nodes.size(0) - 1, nodes.size(1)
+    order = node_sequence.size(1)
+    L = lib()
+    with torch.cuda.device(dev):
+        keep = torch.empty(walks, dtype=torch.int32, device=dev)
+        count = torch.empty(walks, dtype=torch.int32, device=dev)
+        check(L.pp_walk_pack_count(_p(lengths), walks, steps, order, _p(keep), _p(count), _stream()), "pp_walk_pack_count")
+        offset, rank = exclusive_scan(count), exclusive_scan(keep)
+        positions, kept = torch.stack((offset[-1], rank[-1])).tolist()
+        seq = torch.empty((positions, 1), dtype=torch.int64, device=dev)
+        edges = torch.empty((2, positions - kept), dtype=torch.int64, device=dev)
+        dag_nodes = torch.empty(kept, dtype=torch.int64, device=dev)
+        dag_edges = torch.empty(kept, dtype=torch.int64, device=dev)
+        dag_weight = torch.empty(kept, dtype=torch.float32, device=dev)
+        check(L.pp_walk_pack_fill(_p(nodes), _p(lengths), walks, steps, order, n, _p(node_sequence), _p(offset), _p(rank), positions, kept, _p(seq),
+                                  edges[0].data_ptr(), edges[1].data_ptr() if kept else edges.data_ptr(), _p(dag_nodes), _p(dag_edges),
+                                  _p(dag_weight), _stream()), "pp_walk_pack_fill")
+    return WalkStore(seq, edges, dag_nodes, dag_edges, dag_weight)

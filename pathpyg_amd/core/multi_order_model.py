@@ -402,6 +402,17 @@ class MultiOrderModel:
                 accepted = k
         return accepted
 
+    def sample_walks(self, order: int, num_walks: int, steps: int, start="weighted", seed: Optional[int] = None) -> PathData:
+        """``num_walks`` random walks of at most ``steps`` transitions on layer ``order``, weighted by its ``edge_weight``, as first-order
+        sequences in a device-resident :class:`PathData` with layer 1's mapping (:class:`pathpyg_amd.processes.RandomWalk`; walks that
+        could not take a step are dropped).  The null model of :meth:`estimate_order`: walks from layer k carry order k."""
+        from ..processes import RandomWalk
+        if order not in self.layers:
+            raise ValueError(f"the model has no layer of order {order}")
+        layer = self.layers[order]
+        weight = "edge_weight" if "edge_weight" in layer.data else None
+        return RandomWalk(layer, weight=weight, first_order_mapping=self.layers[1].mapping).run(num_walks, steps, start, seed).to_path_data()
+
     def to_dbgnn_data(self, max_order: int = 2, mapping: str = "last", x: torch.Tensor | None = None,
                       x_h: torch.Tensor | None = None) -> Data:
         """Input bundle of :class:`pathpyg_amd.nn.DBGNN` (reference multi_order_model.py:511-554).
