@@ -1281,6 +1281,63 @@ int pp_walk_pack_fill(const int32_t* nodes, const int32_t* lengths, int64_t walk
                       int64_t* seq_out, int64_t* edge_src, int64_t* edge_dst, int64_t* dag_num_nodes, int64_t* dag_num_edges, float* dag_weight,
                       pp_stream_t stream);
 
+/* ------------------------------------------------------------------ distributions and PageRank (pp_graph_diffusion.hip) */
+/* The deterministic half of a random-walk process: B distributions at once, pushed through the transition structure of a Graph or of a layer
+ * of a MultiOrderModel.  The structure is the MERGED one: row_ptr [n + 1] of Graph.simple_successors() and, for the pull, col_ptr [n + 1],
+ * src [k] int64 and perm [k] int64 of Graph.simple_predecessors() (perm[j] = the successor position of pull entry j).  weight [k] float64 in
+ * SUCCESSOR order, NULL = every entry 1.  A block X is [n, B] float64 row-major, B a power of two up to 64 (the padded width; `live` of the
+ * columns count, the others stay as they are); a wider batch runs in column tiles of 64 from the host, which by (b) changes nothing.
+ * All arithmetic is float64 and every operation named below is ONE rounded operation (nothing is contracted).  Pointers are clamped as
+ * everywhere; a source index outside [0, n) adds 0.
+ * Sizes: n, k < 2^31 - 1 and n * B * 8 * (kept blocks) < 2^47 bytes, else PP_ERR_TOO_LARGE before any launch; pp_diffusion_check_sizes is
+ * that test alone (host code).
+ *
+ * pp_diffusion_table: T_u = the left-to-right sum of u's merged entries (s = 0; s = s + w; one lane per row) -> total [n];
+ *   prob[j] = w / T_u for pull entry j of source u, 0 where T_u is 0 -> prob [k]; dangling[u] = !(T_u > 0) -> uint8 [n].  bad [1] int32
+ *   (zeroed by the call) becomes 1 for a negative, NaN or infinite weight or an infinite T_u.
+ * pp_diffusion_run: with s[v] = sum_i prob_i * x[src_i] over v's pull list and D = sum of x[u] over the dangling u, one iteration is
+ *     PP_DIFFUSION_PAGERANK: x'[v] = alpha * (s[v] + D * d[v]) + (1 - alpha) * p[v]        (p, d [n, B]; networkx 3.4's order)
+ *     PP_DIFFUSION_WALK    : x'[v] = lazy * x[v] + (1 - lazy) * (s[v] + (dangling[v] ? x[v] : 0))
+ *   and err_c = sum |x' - x| per column c.  X [kept, n, B]: X[0] holds the start.  kept == 2: the iterates alternate between the two blocks;
+ *   kept == max_iter + 1: iterate t is left in X[t].  A column stops at its FIRST iterate with err_c < threshold (false for a NaN; a negative
+ *   threshold never holds: exactly max_iter iterations) and keeps exactly that iterate whatever the others still do; the run ends when all
+ *   live columns have stopped, or after max_iter >= 0 iterations.  iterations [B], converged [B], where [1], grids [2] are HOST words: per
+ *   column the iterations done and whether the criterion held, the block of X that holds the result, the workgroups of the row and of the
+ *   heavy launch.  tvd (device, [max_iter + 1, B], or NULL; needs target [n]): tvd[t, c] = 0.5 * sum |x_t - target|, t = 0 .. max_iter
+ *   (meant for a negative threshold; a stopped column's later rows are not written).
+ *   Launch scheme: per iteration 2 plain launches, 3 with heavy rows (heavy rows; all rows, update and partials; decide, one workgroup per
+ *   column).  No cooperative launch, no grid-wide barrier, no floating-point atomics (the decide kernel counts its arrived workgroups with
+ *   one integer atomic).  Every kernel reads the run's `done` word first and does nothing once it is set.  The host enqueues `batch`
+ *   iterations (0 = 16; the last batch is cut to what max_iter leaves), synchronises and reads the state words once per batch.
+ *   Summation — the shapes are functions of a row's length, of n and of heavy_min only:
+ *     a row of fewer than heavy_min entries (0 = pp_diffusion_heavy_min() = 1024): entry i of the row into accumulator i mod 4, in order; the
+ *       sum is (a0 + a1) + (a2 + a3).  A row of heavy_min entries or more: chunks of 256 entries, each summed that way, added in order to 0.0;
+ *     D, err, tvd: per range of 256 nodes, each group of 4 consecutive nodes is summed ((t0 + t1) + t2) + t3, the groups are added in order to
+ *       0.0; the ranges are folded by index: thread t of 256 adds ranges t, t + 256, ... in order, then a wave butterfly, the 4 waves in order.
+ *   Properties:
+ *     (a) every output has the same bits on every run;
+ *     (b) the bits of a column do not depend on B, on which columns share its block, or on their values: a lane pair (row, column) does
+ *         the same operations in the same order whatever B is, the partials are per (range, column) and every column is folded and decided
+ *         by a workgroup of its own.  A batch equals its columns run one by one;
+ *     (c) pp_set_launch_share and `batch` change no bit (the grid strides over ranges whose partials do not depend on it);
+ *     (d) max_iter is honoured exactly, also when it is no multiple of the batch.
+ *   ws: pp_diffusion_ws_bytes(n, B).
+ * pp_diffusion_project: out[r, c] = sum of x[idx[i], c] over i in [ptr[r], ptr[r + 1]) (ptr [rows + 1], idx [k] int64 into the n_src rows of
+ *   x [n_src, B]), in the row shapes above: the first-order projection of a layer, with the layer nodes grouped by their last first-order
+ *   node and ascending inside a group.  out [rows, B].  ws: pp_diffusion_ws_bytes(rows, B). */
+enum { PP_DIFFUSION_PAGERANK = 0, PP_DIFFUSION_WALK = 1 };
+int64_t pp_diffusion_heavy_min(void);
+int pp_diffusion_check_sizes(int64_t n, int64_t k, int64_t B, int64_t kept);
+int pp_diffusion_table(const int64_t* row_ptr, const double* weight, const int64_t* src, const int64_t* perm, int64_t n, int64_t k, double* total,
+                       double* prob, uint8_t* dangling, int32_t* bad, pp_stream_t stream);
+size_t pp_diffusion_ws_bytes(int64_t rows, int64_t B);
+int pp_diffusion_run(const int64_t* col_ptr, const int64_t* src, const double* prob, const uint8_t* dangling, int64_t n, int64_t k, int B, int live,
+                     int mode, double alpha, double lazy, const double* p, const double* d, const double* target, double* X, int64_t kept,
+                     double threshold, int64_t max_iter, int64_t batch, int64_t heavy_min, int64_t* iterations, int64_t* converged, int64_t* where,
+                     double* tvd, int64_t* grids, void* ws, size_t ws_bytes, pp_stream_t stream);
+int pp_diffusion_project(const int64_t* ptr, const int64_t* idx, int64_t rows, int64_t n_src, int64_t k, const double* x, int B, double* out,
+                         int64_t heavy_min, void* ws, size_t ws_bytes, pp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,59 @@ def graph_power_centrality(graph, mode: int, threshold: float, max_iter: int, al
     return (values, stats.iterations, stats.converged, stats) if with_stats else (values, stats.iterations, stats.converged)
 
 
+DIFFUSION_PAGERANK, DIFFUSION_WALK = _hip.DIFFUSION_PAGERANK, _hip.DIFFUSION_WALK
+
+
+def graph_diffusion_structure(graph, weight: str | None = None, count_stored: bool = False):
+    """``(col_ptr, src, _hip.DiffusionTable)`` on the compute device: the pull structure of ``graph.simple_predecessors()`` with the transition
+    probabilities of csrc/pp_graph_diffusion.hip.  An entry weighs the edge attribute ``weight`` summed over its parallel edges, or with
+    ``weight=None`` the number of stored edges behind it (``count_stored``: the view of ``RandomWalk``) or 1 (networkx's view).  The caller
+    looks at ``table.bad``.  A CPU-resident graph is staged, as in :func:`graph_components`."""
+    dev = compute_device(graph.data.edge_index)
+    row_ptr, _, _, mult = _graph_simple(graph, dev)
+    col_ptr, src, perm = _stage(dev, *graph.simple_predecessors())
+    if weight is not None:
+        w = graph_entry_weights(graph, weight, dev)
+    else:
+        w = mult.to(torch.float64) if count_stored and mult is not None else None
+    return col_ptr, src, _hip.diffusion_table(row_ptr, w, src, perm, graph.n)
+
+
+def graph_diffusion(structure, n: int, mode: int, start, threshold: float, max_iter: int, alpha: float = 0.0, lazy: float = 0.0, p=None, d=None,
+                    target=None, keep_all: bool = False, want_tvd: bool = False, batch: int = 0, heavy_min: int = 0):
+    """``_hip.DiffusionRun`` of the propagator over ``structure`` (:func:`graph_diffusion_structure`) from the float64 ``[n, B]`` block
+    ``start``; ``p`` and ``d`` (PageRank) have its shape, ``target`` is ``[n]``.  More than 64 columns run in tiles of 64 and are put
+    together: a column's bits do not depend on its tile.  ``batch``, ``heavy_min``: 0 = the library's choice.  CPU blocks are staged."""
+    col_ptr, src, table = structure
+    dev = col_ptr.device
+    same = d is p
+    start, p, d, target = (None if t is None else torch.as_tensor(t).to(dev).to(torch.float64) for t in (start, p, d, target))
+    if same:
+        d = p
+    B, tile = int(start.size(1)), _hip.DIFFUSION_MAX_WIDTH
+    runs = []
+    for c0 in range(0, B, tile):
+        cols = slice(c0, min(c0 + tile, B))
+        p_t = None if p is None else p[:, cols]
+        d_t = p_t if same else (None if d is None else d[:, cols])
+        runs.append(_hip.diffusion_run(col_ptr, src, table, n, mode, start[:, cols], threshold, max_iter, alpha, lazy, p_t, d_t, target,
+                                       keep_all, want_tvd, batch, heavy_min))
+    if len(runs) == 1:
+        return runs[0]
+    return _hip.DiffusionRun(torch.cat([r.final for r in runs], 1), sum((r.iterations for r in runs), []), sum((r.converged for r in runs), []),
+                             torch.cat([r.trajectory for r in runs], 2) if keep_all else None,
+                             torch.cat([r.tvd for r in runs], 1) if want_tvd else None, runs[0].grids)
+
+
+def diffusion_project(ptr, idx, rows: int, x, heavy_min: int = 0):
+    """float64 ``[rows, B]``: the rows ``idx[ptr[r] : ptr[r + 1]]`` of ``x`` (float64 ``[n, B]``) summed per group, in tiles of 64 columns."""
+    dev = compute_device(ptr, idx, x)
+    ptr, idx, x = _stage(dev, ptr, idx, x)
+    tile = _hip.DIFFUSION_MAX_WIDTH
+    outs = [_hip.diffusion_project(ptr, idx, rows, x[:, c0:c0 + tile], heavy_min) for c0 in range(0, int(x.size(1)), tile)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs, 1)
+
+
 def layout_adjacency(edge_index, weight, num_nodes: int):
     """``(ptr, nbr, w)`` on the compute device: the symmetric adjacency the reference's layouts see (csrc/pp_graph_layout.hip) — one entry
     per unordered pair with a stored edge in either direction, valued 1 or, with ``weight`` (one value per stored edge), by the LAST such

@@ -3115,3 +3115,147 @@ def walk_pack(nodes: torch.Tensor, lengths: torch.Tensor, node_sequence: torch.T
                                   edges[0].data_ptr(), edges[1].data_ptr() if kept else edges.data_ptr(), _p(dag_nodes), _p(dag_edges),
                                   _p(dag_weight), _stream()), "pp_walk_pack_fill")
     return WalkStore(seq, edges, dag_nodes, dag_edges, dag_weight)
+
+
+# ------------------------------------------------------------------ distributions and PageRank (csrc/pp_graph_diffusion.hip)
+DIFFUSION_PAGERANK, DIFFUSION_WALK = 0, 1                          # PP_DIFFUSION_* of the header
+DIFFUSION_MAX_WIDTH = 64                                           # columns per launch; a wider batch runs in tiles
+
+
+def diffusion_heavy_min() -> int:
+    """The pull-list length from which the propagator gives a row a whole workgroup (the library's default)."""
+    return int(lib().pp_diffusion_heavy_min())
+
+
+def diffusion_width(columns: int) -> int:
+    """The padded width of a block of ``columns`` (1 .. 64) distributions: the next power of two."""
+    if not 1 <= columns <= DIFFUSION_MAX_WIDTH:
+        raise ValueError(f"a block holds 1 .. {DIFFUSION_MAX_WIDTH} columns, got {columns}")
+    return 1 << (columns - 1).bit_length()
+
+
+def diffusion_check_sizes(n: int, k: int, width: int, kept: int, device=None) -> None:
+    """The size limits of the propagator (host arithmetic, nothing is allocated): raises like the kernels would; with ``device`` also when
+    the ``kept`` blocks are more than that device's memory."""
+    check(lib().pp_diffusion_check_sizes(n, k, width, kept), "pp_diffusion_check_sizes")
+    if device is not None:
+        need, have = n * width * 8 * kept, torch.cuda.get_device_properties(device).total_memory
+        if need > have:
+            raise HipError(f"pp_diffusion_check_sizes failed with status -4: {kept} blocks of {n} x {width} float64 are {need} bytes, the "
+                           f"device has {have}")
+
+
+class DiffusionTable(NamedTuple):
+    total: torch.Tensor          # [n] float64: T_u
+    prob: torch.Tensor           # [k] float64, pull order: w / T_u
+    dangling: torch.Tensor       # [n] uint8: !(T_u > 0)
+    bad: bool                    # a weight was negative or not finite (or a row's sum overflowed)
+
+
+def diffusion_table(row_ptr: torch.Tensor, weight: torch.Tensor | None, src: torch.Tensor, perm: torch.Tensor, n: int) -> DiffusionTable:
+    """The transition table of ``pp_diffusion_table``; one read-back (the flag)."""
+    dev = require_device(row_ptr, weight, src, perm)
+    k = src.numel()
+    if weight is not None and (weight.dtype != torch.float64 or weight.numel() != k):
+        raise ValueError(f"weight must be a float64 vector of {k} entries")
+    if row_ptr.numel() != n + 1 or perm.numel() != k:
+        raise ValueError("row_ptr must have n + 1 entries and perm one per pull entry")
+    row_ptr, src, perm = (t.to(torch.int64).contiguous() for t in (row_ptr, src, perm))
+    weight = None if weight is None else weight.contiguous()
+    with torch.cuda.device(dev):
+        total = torch.empty(n, dtype=torch.float64, device=dev)
+        prob = torch.empty(k, dtype=torch.float64, device=dev)
+        dangling = torch.empty(n, dtype=torch.uint8, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib().pp_diffusion_table(_p(row_ptr), _p(weight), _p(src), _p(perm), n, k, _p(total), _p(prob), _p(dangling), _p(bad), _stream()),
+              "pp_diffusion_table")
+        return DiffusionTable(total, prob, dangling, bool(bad.item()))
+
+
+class DiffusionRun(NamedTuple):
+    final: torch.Tensor          # [n, B] float64: per column the iterate that met the criterion, or the last one
+    iterations: list             # [B] iterations done per column
+    converged: list              # [B] the criterion held
+    trajectory: torch.Tensor | None     # [max_iter + 1, n, B] with keep_all
+    tvd: torch.Tensor | None     # [max_iter + 1, B] with a target
+    grids: tuple                 # workgroups of the row launch and of the heavy launch
+
+
+def diffusion_run(col_ptr: torch.Tensor, src: torch.Tensor, table: DiffusionTable, n: int, mode: int, start: torch.Tensor, threshold: float,
+                  max_iter: int, alpha: float = 0.0, lazy: float = 0.0, p: torch.Tensor | None = None, d: torch.Tensor | None = None,
+                  target: torch.Tensor | None = None, keep_all: bool = False, want_tvd: bool = False, batch: int = 0,
+                  heavy_min: int = 0) -> DiffusionRun:
+    """``pp_diffusion_run`` on one block of at most 64 columns: ``start``, ``p``, ``d`` float64 ``[n, B]``, ``target`` float64 ``[n]``.  A
+    negative ``threshold`` runs exactly ``max_iter`` iterations.  The block is padded to a power of two with zero columns."""
+    if start.dim() != 2 or start.size(0) != n or start.dtype != torch.float64:
+        raise ValueError(f"start must be float64 [n = {n}, B], got {tuple(start.shape)} {start.dtype}")
+    B = int(start.size(1))
+    width = diffusion_width(B)
+    k = src.numel()
+    max_iter = int(max_iter)
+    kept = max_iter + 1 if keep_all else 2
+    for t, name in ((p, "p"), (d, "d")):
+        if t is not None and (t.shape != start.shape or t.dtype != torch.float64):
+            raise ValueError(f"{name} must be float64 {tuple(start.shape)}")
+    if target is not None and (target.dtype != torch.float64 or target.numel() != n):
+        raise ValueError(f"target must be a float64 vector of {n} entries")
+    if mode == DIFFUSION_PAGERANK and (p is None or d is None):
+        raise ValueError("PageRank needs p and d")
+    if want_tvd and target is None:
+        raise ValueError("tvd needs a target")
+    dev = require_device(col_ptr, src, table.prob, table.dangling, start, p, d, target)
+    diffusion_check_sizes(n, k, width, kept, dev)
+    L = lib()
+    with torch.cuda.device(dev):
+        def padded(t):
+            if t is None:
+                return None
+            if width == B:
+                return t.contiguous()
+            out = torch.zeros((n, width), dtype=torch.float64, device=dev)
+            out[:, :B] = t
+            return out
+        X = torch.empty((kept, n, width), dtype=torch.float64, device=dev)
+        if width != B:
+            X[0].zero_()
+        X[0, :, :B] = start
+        p_pad = padded(p)
+        d_pad = p_pad if d is p else padded(d)
+        target = None if target is None else target.reshape(-1).contiguous()
+        tvd = torch.zeros((max_iter + 1, width), dtype=torch.float64, device=dev) if want_tvd else None
+        iterations, converged = (ctypes.c_int64 * width)(), (ctypes.c_int64 * width)()
+        where, grids = ctypes.c_int64(0), (ctypes.c_int64 * 2)()
+        ws = _workspace(L.pp_diffusion_ws_bytes(n, width), dev)
+        check(L.pp_diffusion_run(_p(col_ptr), _p(src), _p(table.prob), _p(table.dangling), n, k, width, B, int(mode), float(alpha), float(lazy),
+                                 _p(p_pad), _p(d_pad), _p(target), _p(X), kept, float(threshold), max_iter, int(batch), int(heavy_min),
+                                 ctypes.addressof(iterations), ctypes.addressof(converged), ctypes.addressof(where), _p(tvd),
+                                 ctypes.addressof(grids), _p(ws), ws.numel(), _stream()), "pp_diffusion_run")
+        final = X[int(where.value), :, :B]
+        return DiffusionRun(final.contiguous() if width != B or not keep_all else final, list(iterations[:B]), [bool(c) for c in converged[:B]],
+                            X[:, :, :B] if keep_all else None, None if tvd is None else tvd[:, :B], (int(grids[0]), int(grids[1])))
+
+
+def diffusion_project(ptr: torch.Tensor, idx: torch.Tensor, rows: int, x: torch.Tensor, heavy_min: int = 0) -> torch.Tensor:
+    """``pp_diffusion_project``: float64 ``[rows, B]`` = the sums of the rows ``idx[ptr[r] : ptr[r + 1]]`` of ``x`` (float64 ``[n_src, B]``,
+    B <= 64)."""
+    if x.dim() != 2 or x.dtype != torch.float64:
+        raise ValueError("x must be float64 [n, B]")
+    n_src, B = int(x.size(0)), int(x.size(1))
+    width = diffusion_width(B)
+    dev = require_device(ptr, idx, x)
+    ptr, idx = ptr.to(torch.int64).contiguous(), idx.to(torch.int64).contiguous()
+    if ptr.numel() != rows + 1:
+        raise ValueError(f"ptr must have rows + 1 = {rows + 1} entries")
+    k = idx.numel()
+    L = lib()
+    with torch.cuda.device(dev):
+        if width != B:
+            xp = torch.zeros((n_src, width), dtype=torch.float64, device=dev)
+            xp[:, :B] = x
+        else:
+            xp = x.contiguous()
+        out = torch.empty((rows, width), dtype=torch.float64, device=dev)
+        ws = _workspace(L.pp_diffusion_ws_bytes(rows, width), dev)
+        check(L.pp_diffusion_project(_p(ptr), _p(idx), rows, n_src, k, _p(xp), width, _p(out), int(heavy_min), _p(ws), ws.numel(), _stream()),
+              "pp_diffusion_project")
+    return out if width == B else out[:, :B].contiguous()

@@ -1,5 +1,5 @@
 """Algorithms on the hot path of pathpyG: order lifts, De Bruijn aggregation, shortest paths and centralities."""
-from . import centrality, components, generative_models, shortest_paths, weisfeiler_leman  # noqa: F401
+from . import centrality, components, generative_models, ranking, shortest_paths, weisfeiler_leman  # noqa: F401
 from .components import connected_components, largest_connected_component  # noqa: F401
 from .weisfeiler_leman import WeisfeilerLeman_test, color_refinement  # noqa: F401
 from .centrality import (  # noqa: F401
@@ -11,6 +11,7 @@ from .centrality import (  # noqa: F401
     path_node_traversals,
     path_visitation_probabilities,
 )
+from .ranking import pagerank, personalized_pagerank  # noqa: F401
 from .lift_order import (  # noqa: F401
     aggregate_edge_index,
     aggregate_node_attributes,

@@ -19,7 +19,8 @@ csrc/pp_graph_paths.hip); the temporal ones live in :mod:`pathpyg_amd.algorithms
 The reference module's ``__getattr__`` forwards every unknown name to ``networkx.algorithms.centrality`` on a Python copy of the graph.
 Two of the measures behind that forwarding are native here: :func:`eigenvector_centrality` and :func:`katz_centrality` run networkx's
 power iterations as pull products over the predecessor lists of the distinct edges, convergence test included, on the GPU
-(``pp_graph_power_iterate``, csrc/pp_graph_power.hip).  The forwarding itself is not ported: this package has no networkx dependency and
+(``pp_graph_power_iterate``, csrc/pp_graph_power.hip).  ``networkx.pagerank`` is not behind that forwarding (it is link analysis, not
+``networkx.algorithms.centrality``): PageRank lives in :mod:`pathpyg_amd.algorithms.ranking`.  The forwarding itself is not ported: this package has no networkx dependency and
 no CPU path, so every other forwarded name — ``degree_centrality`` included — is an ``AttributeError``.
 """
 from __future__ import annotations
@@ -135,9 +136,11 @@ class PowerIterationFailedConvergence(RuntimeError):
     """A power iteration did not meet its criterion within ``max_iter`` iterations (networkx's exception of the same name; this package
     does not depend on networkx, so the class is its own)."""
 
-    def __init__(self, max_iter: int):
+    def __init__(self, max_iter: int, columns: list | None = None):
         self.max_iter = int(max_iter)
-        super().__init__(f"power iteration failed to converge within {self.max_iter} iterations")
+        self.columns = None if columns is None else [int(c) for c in columns]       # a batch: the columns that did not converge
+        super().__init__(f"power iteration failed to converge within {self.max_iter} iterations"
+                         + ("" if columns is None else f" in columns {self.columns}"))
 
 
 def _node_vector(value, n: int, name: str) -> torch.Tensor:

@@ -413,6 +413,42 @@ class MultiOrderModel:
         weight = "edge_weight" if "edge_weight" in layer.data else None
         return RandomWalk(layer, weight=weight, first_order_mapping=self.layers[1].mapping).run(num_walks, steps, start, seed).to_path_data()
 
+    def _layer_walk(self, order: int):
+        """The :class:`~pathpyg_amd.processes.RandomWalk` of layer ``order``, weighted by its ``edge_weight`` if it has one."""
+        from ..processes import RandomWalk
+        if order not in self.layers:
+            raise ValueError(f"the model has no layer of order {order}")
+        layer = self.layers[order]
+        weight = "edge_weight" if "edge_weight" in layer.data else None
+        mapping = self.layers[1].mapping if 1 in self.layers else None
+        return RandomWalk(layer, weight=weight, first_order_mapping=mapping)
+
+    def _first_order_result(self, walk, values: torch.Tensor, return_tensor: bool):
+        first = walk.first_order(values)
+        if return_tensor:
+            return first
+        return {walk.mapping.to_id(i): v for i, v in enumerate(first.tolist())}
+
+    def pagerank(self, order: int, alpha: float = 0.85, **kw):
+        """PageRank of layer ``order`` (:func:`pathpyg_amd.algorithms.pagerank` with the layer's ``edge_weight``; its keyword
+        arguments), projected onto first-order nodes: a layer node's rank goes to its LAST first-order node.  Returns
+        ``{first-order id: float}`` in index order or, with ``return_tensor=True``, the float64 tensor on the compute device."""
+        from ..algorithms.ranking import pagerank
+        return_tensor = bool(kw.pop("return_tensor", False))
+        walk = self._layer_walk(order)
+        kw.setdefault("weight", walk.weight)
+        return self._first_order_result(walk, pagerank(walk.graph, alpha, return_tensor=True, **kw), return_tensor)
+
+    def stationary_distribution(self, order: int, **kw):
+        """The stationary visitation probabilities of layer ``order`` (:meth:`pathpyg_amd.processes.RandomWalk.stationary_distribution`
+        with the layer's ``edge_weight``; its keyword arguments), projected onto first-order nodes.  Returns ``{first-order id: float}``
+        or, with ``return_tensor=True``, the float64 tensor on the compute device."""
+        return_tensor = bool(kw.pop("return_tensor", False))
+        if kw.get("return_iterations"):
+            raise ValueError("return_iterations: ask RandomWalk.stationary_distribution of the layer for the count")
+        walk = self._layer_walk(order)
+        return self._first_order_result(walk, walk.stationary_distribution(**kw), return_tensor)
+
     def to_dbgnn_data(self, max_order: int = 2, mapping: str = "last", x: torch.Tensor | None = None,
                       x_h: torch.Tensor | None = None) -> Data:
         """Input bundle of :class:`pathpyg_amd.nn.DBGNN` (reference multi_order_model.py:511-554).

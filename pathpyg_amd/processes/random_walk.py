@@ -9,7 +9,13 @@ every run, whatever the grid.
 A walk moves from ``v`` along one of its stored out-edges, chosen with probability ``weight / (sum of v's weights)`` (parallel edges are
 separate entries; an edge of weight 0 is never taken), and ends early at a node without an out-edge of positive weight.
 
-Out of scope: restart or teleport, stationary distributions, alias tables, temporal walks on event streams.
+The deterministic half runs on the batched propagator of ``csrc/pp_graph_diffusion.hip`` (the header's "distributions and PageRank" block):
+:meth:`RandomWalk.evolve` pushes B start distributions through the same chain — where the probability mass is after ``t`` steps, the total
+variation distance to a target over time — and :meth:`RandomWalk.stationary_distribution` iterates to the fixed point; both project onto
+first-order nodes (:meth:`RandomWalk.first_order`).  Mass that reaches a node without an out-edge of positive weight stays there, which is
+what :meth:`RandomWalk.run` does with a walk.  Teleport lives in :func:`pathpyg_amd.algorithms.pagerank`.
+
+Out of scope: alias tables, temporal walks on event streams.
 
 Randomness follows :mod:`~pathpyg_amd.algorithms.generative_models`: ``seed=None`` draws one int64 from torch's default CPU generator, so
 ``torch.manual_seed`` makes a script reproducible; the seed used is kept in ``pathpyg_amd.processes.last_seed``.  Negative seeds are taken
@@ -103,7 +109,8 @@ class RandomWalk:
             integers of ``node_sequence``)
 
     The transition table (float64 running sums of every row's weights) is built once, by the first call that needs it, and kept; so are
-    the two start tables.  Restart or teleport, stationary distributions, alias tables and temporal walks on event streams are out of scope.
+    the two start tables, the propagator's pull structure and the first-order grouping.  Alias tables and temporal walks on event streams
+    are out of scope.
     """
 
     def __init__(self, graph: Graph, weight: str | None = None, first_order_mapping: IndexMap | None = None) -> None:
@@ -120,6 +127,8 @@ class RandomWalk:
         self._start_table = None
         self._positive = None
         self._first_order_nodes = None
+        self._structure = None
+        self._grouping = None
 
     # ------------------------------------------------------------------ tables (device)
     def _device_csr(self):
@@ -241,3 +250,214 @@ class RandomWalk:
             positive = self._positive
         nodes, lengths = _hip.walk_run(row_ptr, col, table, n, walks, steps, self.order, seed, mode, given, start_table, positive)
         return WalkBatch(nodes, lengths, node_sequence, n, self.mapping, self._num_first_order)
+
+    # ------------------------------------------------------------------ distributions (csrc/pp_graph_diffusion.hip)
+    def structure(self):
+        """``(col_ptr, src, _hip.DiffusionTable)``: the pull structure of the propagator over the graph's MERGED entries, built on first use
+        and kept.  An entry weighs its parallel edges' weights summed — the number of stored edges behind it with ``weight=None`` — so the
+        chain is the one :meth:`run` samples."""
+        if self._structure is None:
+            structure = _dispatch.graph_diffusion_structure(self.graph, self.weight, count_stored=True)
+            if structure[2].bad:
+                raise ValueError(f"edge attribute {self.weight}: transition weights must be finite and not negative")
+            self._structure = structure
+        return self._structure
+
+    def _first_order_grouping(self):
+        """``(ptr [n1 + 1], order [n])``: the layer nodes grouped by their last first-order node, ascending inside a group (the stable
+        argsort), made once and kept."""
+        if self._grouping is None:
+            last = self._device_csr()[2][:, -1].contiguous()
+            n1 = self._num_first_order()
+            if last.numel() and (_hip.minmax(last)[0] < 0 or _hip.minmax(last)[1] >= n1):
+                raise ValueError(f"node_sequence names first-order nodes outside [0, {n1})")
+            order = _hip.argsort(last, (0, max(n1 - 1, 0))) if last.numel() else last
+            self._grouping = (_hip.ptr_from_sorted(last[order], n1), order)
+        return self._grouping
+
+    def first_order(self, values, *, heavy_min: int = 0) -> torch.Tensor:
+        """The projection of a block on the graph's nodes (``[n]`` or ``[n, B]``) onto first-order nodes: float64 ``[n1]`` / ``[n1, B]`` on the
+        device, ``first[v1] = sum of values[u]`` over the nodes ``u`` whose last first-order node (``node_sequence[u, -1]``) is ``v1``,
+        in ascending ``u``.  The identity for a first-order graph."""
+        values = torch.as_tensor(values)
+        if values.dim() not in (1, 2) or values.size(0) != self.graph.n:
+            raise ValueError(f"values must be [n] or [n, B] with n = {self.graph.n}, got {tuple(values.shape)}")
+        ptr, order = self._first_order_grouping()
+        block = values.reshape(self.graph.n, -1).to(ptr.device).to(torch.float64)
+        if block.size(1) == 0:
+            return torch.empty((self._num_first_order(), 0), dtype=torch.float64, device=ptr.device)
+        out = _dispatch.diffusion_project(ptr, order, self._num_first_order(), block, heavy_min)
+        return out.reshape(-1) if values.dim() == 1 else out
+
+    def _total_weight(self) -> float:
+        """The sum of all T_v, in the fixed shape of the projection kernel (one group that holds every node)."""
+        total = self.structure()[2].total
+        n = total.numel()
+        ptr = torch.tensor([0, n], dtype=torch.int64, device=total.device)
+        return float(_dispatch.diffusion_project(ptr, torch.arange(n, dtype=torch.int64, device=total.device), 1, total.reshape(-1, 1)).item())
+
+    @staticmethod
+    def _start_width(start) -> int:
+        """The number of columns a start argument asks for, from its form alone (host code)."""
+        if isinstance(start, str):
+            if start not in ("weighted", "uniform"):
+                raise ValueError('start: "weighted", "uniform", node indices or ids, or a float [n] / [n, B] distribution')
+            return 1
+        if isinstance(start, (torch.Tensor, np.ndarray)):
+            t = torch.as_tensor(start)
+            if t.dtype.is_floating_point:
+                if t.dim() not in (1, 2):
+                    raise ValueError(f"a start distribution is [n] or [n, B], got {tuple(t.shape)}")
+                return 1 if t.dim() == 1 else int(t.size(1))
+            if t.dim() != 1 or t.dtype == torch.bool:
+                raise ValueError("start: a one-dimensional tensor of node indices")
+            return int(t.numel())
+        if isinstance(start, (list, tuple)):
+            return len(start)
+        raise ValueError('start: "weighted", "uniform", node indices or ids, or a float [n] / [n, B] distribution')
+
+    def _host_start(self, start, name: str = "start"):
+        """A start argument checked on the host, as ``(kind, value, squeeze)``: ``("drawn", "weighted" | "uniform", True)``, ``("indices",
+        int64 [B], False)`` or ``("block", normalised float64 [n, B] on the host, it had no column axis)``."""
+        from ..algorithms.ranking import _checked_weights, normalized_columns
+        n = self.graph.n
+        if isinstance(start, str):
+            return "drawn", start, True
+        if isinstance(start, (torch.Tensor, np.ndarray)) and torch.as_tensor(start).dtype.is_floating_point:
+            t = torch.as_tensor(start).to(torch.float64).cpu()
+            if t.size(0) != n:
+                raise ValueError(f"{name}: a distribution has one entry per node ({n}), got shape {tuple(t.shape)}")
+            return "block", normalized_columns(_checked_weights(t.reshape(n, -1), name), name), t.dim() == 1
+        return "indices", self._explicit_starts(start), False
+
+    def _start_block(self, spec):
+        """``(block float64 [n, B] on the device, squeeze)`` of a checked start (:meth:`_host_start`)."""
+        kind, value, squeeze = spec
+        n = self.graph.n
+        table = self.structure()[2]
+        dev = table.total.device
+        if kind == "block":
+            return value.to(dev), squeeze
+        if kind == "indices":
+            idx = value.to(dev)
+            block = torch.zeros((n, idx.numel()), dtype=torch.float64, device=dev)
+            block[idx, torch.arange(idx.numel(), device=dev)] = 1.0
+            return block, squeeze
+        if value == "weighted":
+            total = self._total_weight()
+            if not total > 0.0:
+                raise ValueError("no node has an out-edge of positive weight: there is nowhere to start")
+            return (table.total / total).reshape(n, 1), squeeze
+        positive = table.total > 0
+        count = int(positive.sum().item())
+        if count == 0:
+            raise ValueError("no node has an out-edge of positive weight: there is nowhere to start")
+        return (positive.to(torch.float64) * (1.0 / count)).reshape(n, 1), squeeze
+
+    def _check_process(self, start, lazy, kept: int, name: str = "start"):
+        """The refusals that need no device — the forms and values of the arguments, the sizes by arithmetic (nothing is allocated) — and
+        ``(lazy, the checked start)``."""
+        if isinstance(lazy, bool) or not isinstance(lazy, (int, float, np.integer, np.floating)) or not 0.0 <= float(lazy) <= 1.0:
+            raise ValueError(f"lazy must lie in [0, 1], got {lazy!r}")
+        g = self.graph
+        if g.n == 0:
+            raise ValueError("the graph has no nodes: there is no distribution on it")
+        width = self._start_width(start)
+        if width == 0:
+            raise ValueError(f"{name} names no distribution")
+        _hip.diffusion_check_sizes(g.n, int(g.data.peek("edge_index").shape[1]), _hip.diffusion_width(min(width, _hip.DIFFUSION_MAX_WIDTH)), kept)
+        return float(lazy), self._host_start(start, name)
+
+    def evolve(self, start, steps: int, *, lazy: float = 0.0, target=None, keep_all: bool = False, batch: int = 0,
+               heavy_min: int = 0) -> "Evolution":
+        """Where the probability mass is after ``steps`` steps of the walk: every start distribution ``x`` is pushed through
+        ``x'[v] = lazy * x[v] + (1 - lazy) * (sum_u P[u, v] x[u] + (x[v] if v is dangling))``, ``P[u, v] = w(u, v) / T_u``; a node without
+        an out-edge of positive weight is dangling and keeps its mass, as :meth:`run` leaves a walk there.  All ``steps`` iterations are
+        enqueued with one synchronisation at the end.
+
+        Args:
+            start: ``"weighted"``: ``T_v / sum T``; ``"uniform"``: ``1 / #nodes with T_v > 0`` on those nodes; a tensor / array of node
+                INDICES or a list of node IDS: one one-hot column each; a float ``[n]`` or ``[n, B]`` tensor / array: distributions, not
+                negative and finite, normalised per column (``ValueError`` for an all-zero column)
+            steps: the number of iterations, >= 0
+            lazy: the probability of staying put in a step, in [0, 1]
+            target: a float ``[n]`` distribution (normalised) or ``"stationary"`` (:meth:`stationary_distribution`, computed with this
+                ``lazy``, or with 0.5 if it is 0: the fixed point is the same and periodic chains converge): switches ``tvd`` on
+            keep_all: keep every iterate
+            batch, heavy_min: kernel settings (0 = the library's choice); they change no bit, respectively only the shape of long rows' sums
+        """
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+            raise ValueError("steps must be an integer >= 0")
+        steps = int(steps)
+        lazy, spec = self._check_process(start, lazy, steps + 1 if keep_all else 2)
+        if isinstance(target, str):
+            if target != "stationary":
+                raise ValueError('target: a float [n] distribution or "stationary"')
+        elif target is not None:
+            t = torch.as_tensor(target) if isinstance(target, (torch.Tensor, np.ndarray)) else None
+            if t is None or t.dim() != 1 or not t.dtype.is_floating_point:
+                raise ValueError("target: a float [n] distribution or \"stationary\"")
+            target = self._host_start(t, "target")[1].reshape(-1)
+        n = self.graph.n
+        block, squeeze = self._start_block(spec)
+        if isinstance(target, str):
+            target = self.stationary_distribution(lazy=lazy if lazy > 0.0 else 0.5)
+        run = _dispatch.graph_diffusion(self.structure(), n, _dispatch.DIFFUSION_WALK, block, -1.0, steps, lazy=lazy, target=target,
+                                        keep_all=keep_all, want_tvd=target is not None, batch=batch, heavy_min=heavy_min)
+        return Evolution(self, run, squeeze, steps)
+
+    def stationary_distribution(self, *, lazy: float = 0.0, tol: float = 1e-12, max_iter: int = 10000, nstart=None, return_iterations: bool = False,
+                                batch: int = 0, heavy_min: int = 0):
+        """The stationary visitation probabilities: the iteration of :meth:`evolve` from ``nstart`` (its ``start`` forms; default
+        ``"weighted"``) until ``sum |x' - x| < tol``.  Float64 ``[n]`` on the device (``[n, B]`` for a start with a column axis); with
+        ``return_iterations`` the iteration count follows (a list for ``[n, B]``).  Raises
+        :class:`~pathpyg_amd.algorithms.centrality.PowerIterationFailedConvergence` after ``max_iter`` iterations.
+
+        The result is the LIMIT FROM THAT START.  It is the unique stationary distribution if the chain is strongly connected and
+        aperiodic; otherwise it depends on the start (mass in different closed classes, or on dangling nodes, stays apart), and a periodic
+        chain may not converge at all — ``lazy > 0`` removes periodicity without moving the fixed point (``x P = x`` iff
+        ``lazy x + (1 - lazy) x P = x``), at the price of more iterations."""
+        from ..algorithms.centrality import PowerIterationFailedConvergence
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)) or max_iter < 1:
+            raise ValueError(f"max_iter must be an integer >= 1, got {max_iter!r}")
+        if not float(tol) > 0.0:
+            raise ValueError(f"tol must be positive, got {tol!r}")
+        start = "weighted" if nstart is None else nstart
+        lazy, spec = self._check_process(start, lazy, 2, "nstart")
+        block, squeeze = self._start_block(spec)
+        run = _dispatch.graph_diffusion(self.structure(), self.graph.n, _dispatch.DIFFUSION_WALK, block, float(tol), int(max_iter), lazy=lazy,
+                                        batch=batch, heavy_min=heavy_min)
+        failed = [c for c, ok in enumerate(run.converged) if not ok]
+        if failed:
+            raise PowerIterationFailedConvergence(max_iter, None if squeeze else failed)
+        values = run.final.reshape(-1) if squeeze else run.final
+        if return_iterations:
+            return values, (run.iterations[0] if squeeze else run.iterations)
+        return values
+
+
+class Evolution:
+    """What :meth:`RandomWalk.evolve` returns, on the device.
+
+    ``final``: float64 ``[n, B]``, ``[n]`` for a string or one-dimensional start.  ``trajectory``: ``[steps + 1, n, B]`` (``[steps + 1, n]``)
+    with ``keep_all``, else ``None``.  ``tvd``: ``[steps + 1, B]`` (``[steps + 1]``), ``tvd[t] = 0.5 * sum |x_t - target|``, with a target,
+    else ``None``.  ``iterations`` = ``steps``."""
+
+    def __init__(self, walk: RandomWalk, run, squeeze: bool, steps: int) -> None:
+        self._walk = walk
+        self.iterations = steps
+        self.final = run.final.reshape(-1) if squeeze else run.final
+        self.trajectory = run.trajectory
+        self.tvd = run.tvd
+        if squeeze:
+            self.trajectory = None if run.trajectory is None else run.trajectory[:, :, 0]
+            self.tvd = None if run.tvd is None else run.tvd[:, 0]
+
+    def first_order(self, trajectory: bool = False) -> torch.Tensor:
+        """``final`` — with ``trajectory=True`` every kept iterate — projected onto first-order nodes (:meth:`RandomWalk.first_order`):
+        ``[n1, B]`` / ``[steps + 1, n1, B]``, without the column axis where ``final`` has none."""
+        if not trajectory:
+            return self._walk.first_order(self.final)
+        if self.trajectory is None:
+            raise ValueError("the trajectory was not kept: evolve(..., keep_all=True)")
+        return torch.stack([self._walk.first_order(x) for x in self.trajectory])
